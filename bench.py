@@ -108,7 +108,54 @@ def parse_args(argv=None):
     ap.add_argument("--in-flight", type=int, default=2,
                     help="contexts (own stream + scratch each) a rank's batch alternates over: with 2, one pair's "
                          "pre-pass and launch gaps run beside the other pair's search")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the float32 disparity maps the last timed step computed "
+                         "(rank 0's batch) as DIR/<name>.npy, at most 64 MB in all: see dump_outputs()")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: everything written together stays below this
+DUMP_SAMPLE_BYTES = 8 << 20    # ... of which the per-pair sample of the whole batch takes at most this
+DUMP_WHOLE_MAPS = 8            # ... and the rest whole maps, at most this many
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, outs):
+    """Write what the caller of the timed path holds after the last timed step: `outs` are the float32 maps
+    (device tensors, batch order) ws_search_device filled.  Inputs depend on the arguments alone, so two builds run
+    with the same arguments are compared file for file.  A batch is far larger than DUMP_BYTES, so:
+      disparity_pair<k>.npy   whole maps of pair 0 and of a fixed, seeded choice of further pairs, while they fit;
+      disparity_sample.npy    1-D: from every pair of the batch in order, its values at seeded flat positions.
+    Returns {file name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    n = len(outs)
+    per_pair = max(1, min(min(o.numel() for o in outs), DUMP_SAMPLE_BYTES // 4 // n))
+    picks = []
+    for o in outs:
+        idx = torch.from_numpy(rng.integers(0, o.numel(), size=per_pair, dtype=np.int64)).to(o.device)
+        picks.append(o.reshape(-1).index_select(0, idx))
+    sample = torch.cat(picks).cpu().numpy().astype(np.float32, copy=False)
+    written = {"disparity_sample.npy": list(sample.shape)}
+    np.save(os.path.join(directory, "disparity_sample.npy"), sample)
+    budget = DUMP_BYTES - sample.nbytes - 64 * 1024          # (headers)
+    order = [0] + [int(k) + 1 for k in rng.permutation(n - 1)]
+    for k in order:
+        if len(written) > DUMP_WHOLE_MAPS:
+            break
+        nbytes = outs[k].numel() * 4
+        if nbytes > budget:
+            continue
+        name = "disparity_pair%d.npy" % k
+        np.save(os.path.join(directory, name), outs[k].cpu().numpy().astype(np.float32, copy=False))
+        written[name] = list(outs[k].shape)
+        budget -= nbytes
+    return written
 
 
 def launch_ranks(n, argv):
@@ -157,6 +204,8 @@ def main():
     # step is a stand-in (CPU test of the launcher and the rank plumbing).  Never for reported numbers.
     rehearse = os.environ.get("WS_BENCH_REHEARSE", "")
     dry = rehearse == "dry"
+    if dry and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs a device (the rehearsal's stand-in step computes nothing)")
 
     import torch
     if not dry and not torch.cuda.is_available():
@@ -174,6 +223,14 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
 
+    def rank_barrier():
+        # barrier() asks torch for the machine's accelerator, which starts the HIP runtime and opens the GPU; the dry
+        # rehearsal touches no device (any number of its ranks may run beside GPU jobs), so it meets on a CPU all_reduce
+        if dry:
+            dist.all_reduce(torch.zeros(1))
+        else:
+            dist.barrier()
+
     import stereo_reconstruction_amd as ws
     from stereo_reconstruction_amd.synthetic import make_pair
     # the extension normally travels with the tree; a tree without it gets it built once per node
@@ -182,7 +239,7 @@ def main():
         if local_rank == 0:
             ws_build.build()
         if dist is not None:
-            dist.barrier()
+            rank_barrier()
     dev = torch.device("cpu") if dry else torch.device("cuda", local_rank)
     in_flight = max(1, args.in_flight)
     ctxs = [] if dry else [ws.WindowSearch(local_rank) for _ in range(in_flight)]
@@ -249,7 +306,7 @@ def main():
     def barrier():
         sync()
         if dist is not None:
-            dist.barrier()
+            rank_barrier()
         sync()
 
     for _ in range(args.warmup):
@@ -268,6 +325,11 @@ def main():
         elapsed = float(t.item())
 
     value = hyps_total * args.steps / elapsed / 1e6     # H*W*D hypotheses of the whole job
+
+    # the last timed step's maps, before anything below searches into the same buffers again
+    dumped = None
+    if args.dump_outputs and rank == 0 and pairs:
+        dumped = dump_outputs(args.dump_outputs, [to for _, _, to in pairs])
 
     # dominant kernel, timed alone with HIP events on the launch stream: every pair of this rank
     reps = max(1, min(args.steps, 20))
@@ -396,6 +458,9 @@ def main():
             out["value_single_pair"] = round(float(width) * height * max_d / single_pair_ms / 1e3, 1)
             out["single_pair"] = {"ms_per_pair": round(single_pair_ms, 4), "what": "one context, one pair after the other "
                                   "(--in-flight 1 semantics; BENCH_r01 timed this way), after the timed region as warm-up"}
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                                   "what": "the last timed step's float32 maps of rank 0's batch (bench.dump_outputs)"}
         if batch or world > 1:
             out["per_rank"] = [{"rank": s["rank"], "items": s["items"], "kernel_ms_sum": s["kernel_ms_sum"],
                                 "wall_ms": s["wall_ms"], "Mdisp_map": round(s["map_hyps"] / 1e6, 1),
@@ -422,7 +487,7 @@ def main():
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
-        dist.barrier()
+        rank_barrier()
         dist.destroy_process_group()
 
 

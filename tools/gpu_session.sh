@@ -1,8 +1,8 @@
 #!/bin/bash
 # One GPU session step with its post-mortem: runs the command from the repo root (under `timeout -k 10`), logs to
 # gpurun_out/<name>.txt, and -- if the runtime left a GPU core dump (a "Memory access fault by GPU" does:
-# "GPU core dump created: gpucore.N") -- opens it with rocgdb in batch mode and keeps the text next to the log, so
-# that the faulting agent, wave, PC and kernel are on record without running anything again (round 3 lost gpucore.919
+# "GPU core dump created: gpucore.N") -- names it in the log (its cause is found with a printf / assert in the kernel
+# or a rocprofv3 kernel trace, never a debugger on the GPU), so the fault is on record (round 3 lost gpucore.919
 # by never looking at it).  The dump itself stays on the box (it can exceed what gpurun merges back).
 #   usage: tools/gpu_session.sh <name> <seconds> <command ...>
 set -u
@@ -15,13 +15,8 @@ rc=$?
 echo "[gpu_session] exit code $rc" >> "$log"
 shopt -s nullglob
 for core in gpucore.* /tmp/gpucore.* "$HOME"/gpucore.*; do
-    out=gpurun_out/$name.$(basename "$core").rocgdb.txt
-    {
-        echo "# $core ($(stat -c %s "$core") bytes), left by: $*"
-        timeout -k 5 180 /opt/rocm/bin/rocgdb -batch -ex "core-file $core" -ex "info agents" -ex "info queues" \
-            -ex "info dispatches" -ex "info threads" -ex "thread apply all bt 4" -ex "info sharedlibrary" /usr/bin/python3 2>&1 | tail -n 400
-    } > "$out"
-    echo "[gpu_session] GPU core dump $core -> $out" >> "$log"
+    case "$core" in *.seen) continue ;; esac
+    echo "[gpu_session] GPU core dump $core ($(stat -c %s "$core") bytes), after: $*" >> "$log"
     mv "$core" "$core.seen" 2>/dev/null
 done
 tail -n 40 "$log"
