@@ -9,6 +9,8 @@ The functions mirror the reference's call surface:
   block_right  ~ ...computeDisparityMapRight(s, varBlock, thres)             (BlockSearch.cpp:88-179)
   linear       ~ LinearSearch(L,R).computeDisparityMap(s)                    (LinearSearch.cpp:10-59)
   evaldisp     ~ evaldisp(disp, gt, mask, badthresh, maxdisp, rounddisp)     (utils.cpp:123-168)
+  fast_left / fast_right: block_left / block_right bit for bit, in O(H * W * D) whatever the window
+    size (oracle/ws_fast.c): whole full-size maps in seconds; no var_block
 Images are H x W x 3 uint8 arrays (BGR), outputs float64 maps.
 """
 import ctypes
@@ -53,7 +55,7 @@ def build(force=False):
     """Compile libws_oracle.so with the Makefile next to this file.  The library is built with
     -march=native, so it is rebuilt when it is older than its sources OR was built on another CPU
     (the .so travels to the GPU box with the tree; its build host's signature sits beside it)."""
-    src = [os.path.join(_HERE, "ws_oracle.c"), os.path.join(_HERE, "ws_oracle.h"), os.path.join(_HERE, "Makefile")]
+    src = [os.path.join(_HERE, f) for f in ("ws_oracle.c", "ws_oracle.h", "ws_fast.c", "ws_fast.h", "Makefile")]
     sig_path, sig = _LIB_PATH + ".host", _host_signature()
     try:
         built_on = open(sig_path).read().strip()
@@ -95,6 +97,10 @@ def lib():
                                     ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         _lib.wso_centred_norm.argtypes = [P(_Image)] + [ctypes.c_int] * 4
         _lib.wso_centred_norm.restype = ctypes.c_double
+        _lib.wsf_block_left.argtypes = [P(_Image), P(_Image)] + [ctypes.c_int] * 3 + [
+            ctypes.c_double] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        _lib.wsf_block_right.argtypes = [P(_Image), P(_Image)] + [ctypes.c_int] * 3 + [
+            ctypes.c_double] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         _lib.wso_evaldisp.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [
             ctypes.c_float, ctypes.c_float, ctypes.c_int, P(ctypes.c_double)]
     return _lib
@@ -110,12 +116,28 @@ def _img(a):
 def _check(rc):
     if rc == -2:
         raise OracleGeometryError("reference would throw cv::Exception (ROI outside image)")
+    if rc == -4:
+        raise NotImplementedError("the fast reference does not implement these arguments (var_block, or window "
+                                  "sums past 32 bits)")
     if rc != 0:
         raise ValueError("oracle rejected the arguments (code %d)" % rc)
 
 
 def _rows(rows, h):
     return (0, h) if rows is None else (int(rows[0]), int(rows[1]))
+
+
+def host_threads():
+    """CPUs this process may really use: the affinity mask capped by the cgroup CPU quota (OpenMP's default counts
+    every core of the machine, and an oversubscribed team spins in its barriers)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) / int(period))))
+    except (OSError, ValueError):
+        pass
+    return max(1, n)
 
 
 def set_threads(n):
@@ -149,6 +171,33 @@ def block_right(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
                                  thres, COST[cost], int(subpixel), y0, y1,
                                  out.ctypes.data, out.shape[1], ctypes.byref(mb)))
     return (out, mb.value) if return_max_block else out
+
+
+def fast_left(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
+              cost="ssd", subpixel=False, rows=None, threads=0):
+    """block_left's map, computed by the fast reference (threads 0: the CPUs this process may use)."""
+    La, Li = _img(L)
+    Ra, Ri = _img(R)
+    out = np.zeros((La.shape[0], La.shape[1]), dtype=np.float64)
+    y0, y1 = _rows(rows, La.shape[0])
+    _check(lib().wsf_block_left(ctypes.byref(Li), ctypes.byref(Ri), block_size,
+                                min_disparity, max_disparity, smooth, COST[cost],
+                                int(subpixel), y0, y1, out.ctypes.data, out.shape[1], int(threads or host_threads())))
+    return out
+
+
+def fast_right(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
+               var_block=False, cost="ssd", subpixel=False, rows=None, threads=0):
+    """block_right's map, computed by the fast reference; var_block raises NotImplementedError."""
+    La, Li = _img(L)
+    Ra, Ri = _img(R)
+    out = np.zeros((Ra.shape[0], Ra.shape[1]), dtype=np.float64)
+    y0, y1 = _rows(rows, Ra.shape[0])
+    _check(lib().wsf_block_right(ctypes.byref(Li), ctypes.byref(Ri), block_size,
+                                 min_disparity, max_disparity, smooth, int(var_block),
+                                 COST[cost], int(subpixel), y0, y1,
+                                 out.ctypes.data, out.shape[1], int(threads or host_threads())))
+    return out
 
 
 def linear(L, R, smooth=1.0, search_range=200, rows=None, threads=1):

@@ -109,6 +109,16 @@ static double march_model_cost(const Canon &c, MarchShape sh)
 // small.  Checked against profiles/r03/nd_grid.txt (1500 x 1000, windows 5 .. 17,
 // D = 128 / 256 / 512, both costs, either instantiation forced) and at 900 x 750 and 2964 x 1988
 // (profiles/r03/nd_rule_check.txt).
+// Does an SSD window's key -- (sum b^2 - 2 sum a.b) << log2(nd), i.e. the SSD minus the reference window's sum of
+// squares -- stay inside (-2^28, 2^28) with nd tags per thread?  Per channel b^2 - 2ab = (b - a)^2 - a^2 lies in
+// [-255^2, 255^2] for plain bytes (bounded by 2 * 255^2 here, as ssd_needs_centring does) and in
+// [-128^2, 255^2 - 127^2] for centred ones (a = 127, b = -128 gives the top: a reference 255 against a target 0).
+static bool ssd_key_fits(int ww, int wh, int nd)
+{
+    const long long per = ssd_needs_centring(ww, wh, nd) ? 255 * 255 - 127 * 127 : 2 * 255 * 255;
+    return per * ww * wh * 3 * nd < (long long)kValidKeyBound;
+}
+
 static MarchShape march_shape(const Canon &c)
 {
     static const MarchShape forced = [] {
@@ -130,7 +140,10 @@ static MarchShape march_shape(const Canon &c)
     const int key[9] = {c.ox1 - c.ox0, c.oy1 - c.oy0, c.d_hi - c.d_lo + 1, c.ww, c.wh, c.ssd, 1, g_model_cus, 0};
     for (const Memo &m : memo)
         if (!memcmp(m.key, key, sizeof key)) return m.shape;
-    const MarchShape sh = march_model_cost(c, kShapeNarrow) < march_model_cost(c, kShapeWide) ? kShapeNarrow : kShapeWide;
+    MarchShape sh = march_model_cost(c, kShapeNarrow) < march_model_cost(c, kShapeWide) ? kShapeNarrow : kShapeWide;
+    // (centred SSD windows of 16 x 16 and more: a maximum-contrast window's key needs the narrower shape's 2 tag bits)
+    if (c.ssd && same_shape(sh, kShapeWide) && !ssd_key_fits(c.ww, c.wh, kShapeWide.nd) && ssd_key_fits(c.ww, c.wh, kShapeNarrow.nd))
+        sh = kShapeNarrow;
     memcpy(memo[next].key, key, sizeof key);
     memo[next].shape = sh;
     next = (next + 1) & 3;
@@ -188,11 +201,10 @@ bool march_supported(const Canon &c)
     const int dcount = c.d_hi - c.d_lo + 1;
     if (dcount < 1) return false;
     // keys must stay inside (-2^28, 2^28)
-    //   SSD: (2 * cross sum) << log2(ND)        SAD: window sum << tag bits
+    //   SSD: (sum b^2 - 2 cross sum) << log2(ND) (ssd_key_fits)        SAD: window sum << tag bits
     if (!c.ssd && march_pk_window(c.ww, c.wh)) return dcount <= 65536; // packed SAD: 16-bit cost, 16-bit global tie tag
-    const long long worst = c.ssd ? 2LL * c.ww * c.wh * 3 * (march_centred(c) ? 128 * 128 : 255 * 255) * march_nd(c)
-                                  : ((long long)c.ww * c.wh * 3 * 255) << tag_bits_for(c);
-    return worst < (long long)kValidKeyBound;
+    if (c.ssd) return ssd_key_fits(c.ww, c.wh, march_nd(c));
+    return (((long long)c.ww * c.wh * 3 * 255) << tag_bits_for(c)) < (long long)kValidKeyBound;
 }
 
 static int march_slots_per_cu(const Canon &c, int nd, int threads, bool halo)

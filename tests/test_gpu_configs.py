@@ -1,5 +1,5 @@
 """BASELINE.json configs that round 1 left without a device test: config 4 (the 15 trainingH shapes,
-batched and device-resident), config 5 WITH the sub-pixel refine at D = 1024 (two d-group passes
+batched and device-resident), config 5 WITH the sub-pixel refine at D = 1024 (four d-group passes
 meeting in the key plane before the parabola), and a MotorcycleE-shaped unequal pair at full size
 (results/Rectified/trainingH/MotorcycleE: 1481 x 1038 left, 1495 x 1052 right, SURVEY.md section 2
 row 15).  Full maps are checked through size-independent properties, oracle row bands bit for bit.
@@ -108,14 +108,14 @@ def test_config4_training_h_shapes(wslib, gpu_ctx, oracle, dmode):
 
 
 def test_config5_subpixel_at_full_size(wslib, gpu_ctx, oracle):
-    """BASELINE.json configs[4]: 3840 x 2160, 9x9 SSD, D = 1024, parabolic refine.  D = 1024 runs as two
+    """BASELINE.json configs[4]: 3840 x 2160, 9x9 SSD, D = 1024, parabolic refine.  D = 1024 runs as four
     d-group passes whose keys meet in a plane (ws_march.hip) BEFORE the refine reads the winner: the
     integer part must be the bit-exact argmin (BlockSearch.cpp:76-82), the fraction within 1e-4."""
     w, h, bs, maxd = 3840, 2160, 9, 1024
     half = 4
     left, right, gt = make_pair(w, h, maxd, 5)
     p = wslib.make_params(wslib.VIEW_LEFT, bs, 0, maxd, 1.0, "ssd")
-    assert wslib.plan(p, left.shape, right.shape)["passes"] >= 2
+    assert wslib.plan(p, left.shape, right.shape)["passes"] == 4
     whole = wslib.BlockSearch(left, right, bs, 0, maxd, cost="ssd", context=gpu_ctx).computeDisparityMapLeft(1.0)
     sub = wslib.BlockSearch(left, right, bs, 0, maxd, cost="ssd", subpixel=True, context=gpu_ctx).computeDisparityMapLeft(1.0)
     assert "march" in gpu_ctx.last_launch()["kernel"]

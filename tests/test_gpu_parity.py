@@ -69,7 +69,7 @@ def test_halo_exchange_sad_kernels(wslib, gpu_ctx, oracle, view, bs):
     from the thread to the right (march_pk_halo, 16 disparities per thread); tiles overlap by one run.  The planner
     takes that kernel where the chip is full (a small search is quicker with the plain one's wider workgroups), so the
     images here are large and the oracle checks row bands over the full width: every tile seam, the image's left edge
-    (masked candidates), ties (few grey levels), two d-group passes, 8 runs per tile."""
+    (masked candidates), ties (few grey levels), several d-group passes (D = 1024), 8 runs per tile."""
     import torch
     rng = np.random.default_rng(bs)
 

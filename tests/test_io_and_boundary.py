@@ -85,6 +85,24 @@ def test_plan_covers_the_baseline_configs(wslib):
     assert ws.plan(ws.make_params(ws.VIEW_LEFT, 21, 0, 64), (100, 200), (100, 200))["marching"] == 0
 
 
+def test_planned_ssd_keys_stay_inside_the_valid_bound(wslib):
+    """A marching SSD key is (sum b^2 - 2 sum a.b) << log2(disparities per thread) and must stay below 2^28 for every
+    pair of images: per channel at most 2 * 255^2 (the plain bytes' bound) or, centred, 255^2 - 127^2.  Regression: the
+    16 x 16 and 17 x 17 windows used to be planned with 8 disparities per thread, whose centred keys pass 2^28 at
+    maximum contrast (tests/test_gpu_whole_map.py shows the wrong maps)."""
+    for view in (wslib.VIEW_LEFT, wslib.VIEW_RIGHT):
+        for bs in range(3, 18, 2):
+            ww = bs if view == wslib.VIEW_LEFT else bs - 1
+            for w, h, maxd in ((400, 116, 512), (1482, 994, 200), (3840, 2160, 1024), (300, 60, 64), (2600, 20, 2500)):
+                p = wslib.plan(wslib.make_params(view, bs, 0, maxd, 1.0, "ssd"), (h, w, 3), (h, w, 3))
+                if not p["marching"]:
+                    continue
+                nd = p["d_per_thread"]
+                centred = 2 * ww * ww * 3 * 255 * 255 * nd >= 1 << 28
+                per = 255 * 255 - 127 * 127 if centred else 2 * 255 * 255
+                assert per * ww * ww * 3 * nd < 1 << 28, (view, bs, w, h, maxd, p)
+
+
 def test_pfm_round_trip_and_orientation(wslib, tmp_path):
     want = np.load(os.path.join(GOLDEN, "teddy_disp0GT_crop.npy"))
     got = wslib.read_pfm(os.path.join(GOLDEN, "teddy_disp0GT_crop.pfm"))
