@@ -356,7 +356,6 @@ hipError_t launch_generic(const GenericArgs &g, hipStream_t s)
 // once (pixel dword + its sum of squares), and every thread sweeps its candidates from there:
 // (a-b)^2 summed over the channels = a.a + b.b - 2 a.b, one v_dot4 per candidate.
 // ------------------------------------------------------------------------------------------
-constexpr int kLinearMaxRange = 4096;
 
 __global__ void __launch_bounds__(256) ws_linear_kernel(const GenericArgs g)
 {

@@ -890,7 +890,8 @@ int run_search(ws_context *ctx, const ws_params *p, const ws_image *L, const ws_
         ctx->last_wgs = m.tiles * m.strips;
         ctx->last_lds = (int)m.lds_bytes;
     } else {
-        ctx->last_kernel = p->view == WS_VIEW_LINEAR ? "ws_linear_kernel" : "ws_generic_kernel";
+        // (launch_linear hands ranges beyond kLinearMaxRange to the brute-force kernel: name the one that runs)
+        ctx->last_kernel = p->view == WS_VIEW_LINEAR && p->linear_range <= kLinearMaxRange ? "ws_linear_kernel" : "ws_generic_kernel";
         ctx->last_threads = 256;
         ctx->last_wgs = ((ow + 255) / 256) * (p->view == WS_VIEW_LEFT ? L->height : R->height);
         ctx->last_lds = 0;

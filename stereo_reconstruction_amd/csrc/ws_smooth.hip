@@ -512,7 +512,7 @@ __global__ void __launch_bounds__(64) ws_smooth_resolve_wave_kernel(float *out, 
 //     untouched candidates in the reference's order (cost ascending, then d descending), kept per
 //     pixel by ws_left_top3_kernel.  For s >= 1 an unlisted neighbour value cannot win at all.
 // Pixel (y, x) needs (y-1, x) and (y, x-1): all pixels of an anti-diagonal x + y = k are
-// independent.  Bands of 64 rows, one wave each on its own CU, walk the diagonals
+// independent.  Bands of 32 rows (kBandRows), one wave each on its own CU, walk the diagonals
 // (ws_smooth_left_bands_kernel): the upper neighbour's value arrives from the lane above one step
 // earlier, the left one is the lane's own previous result, and the window distance of a neighbour's
 // value is a SLIDING sum (the cost at x-1 plus one window column entering, one leaving -- or the cost

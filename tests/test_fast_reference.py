@@ -197,3 +197,34 @@ def test_var_block_is_refused_not_approximated(oracle):
     left, right, _ = make_pair(40, 20, 8, 1)
     with pytest.raises(NotImplementedError):
         oracle.fast_right(left, right, 5, 0, 8, var_block=True)
+
+
+def _tall_tie_pair(rng, w, h, period):
+    """Few-level content of horizontal period `period` plus independent noise in each image: the candidates d = 0,
+    period, 2 period, ... cost nearly the same, so the factor decides often; a black column gives a zero run down
+    every row (the right view's factor acts on d = 0 beside a stored 0)."""
+    tile = rng.integers(0, 3, size=(h, period, 3)) * 60 + 40
+    tex = tile[:, np.arange(w) % period]
+    left = (tex + rng.integers(0, 4, size=tex.shape)).astype(np.uint8)
+    right = (tex + rng.integers(0, 4, size=tex.shape)).astype(np.uint8)
+    left[:, w // 2] = 0
+    right[:, w // 3] = 0
+    return left, right
+
+
+@pytest.mark.parametrize("view", ["left", "right"])
+def test_smooth_raster_pass_over_many_rows(oracle, view):
+    """The smoothFactor pass decides each row serially, over every candidate, from the row above: tall narrow images
+    (150-300 rows, across several multiples of 16, 32 and 64) pin that loop to the oracle over long runs of rows."""
+    rng = np.random.default_rng(5 if view == "left" else 6)
+    fast = oracle.fast_left if view == "left" else oracle.fast_right
+    block = oracle.block_left if view == "left" else oracle.block_right
+    for (w, h, bs, maxd, cost) in ((48, 150, 5, 24, "ssd"), (36, 231, 7, 20, "sad"), (30, 300, 3, 16, "ssd")):
+        left, right = _tall_tie_pair(rng, w, h, 5)
+        plain = fast(left, right, bs, 0, maxd, cost=cost)
+        for s in (0.9, 1.7, -0.5, np.inf):
+            want = block(left, right, bs, 0, maxd, smooth=s, cost=cost)
+            assert not np.array_equal(want, plain), (w, h, s)                 # the factor decided somewhere
+            assert (want[h - 40:] != plain[h - 40:]).any(), (w, h, s)         # ... and still near the bottom
+            got = fast(left, right, bs, 0, maxd, smooth=s, cost=cost)
+            assert np.array_equal(got, want), (view, w, h, bs, maxd, cost, s, np.argwhere(got != want)[:5].tolist())

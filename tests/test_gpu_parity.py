@@ -913,8 +913,8 @@ def test_host_call_in_bands_equals_the_plain_call(wslib, oracle, view):
 
 @pytest.mark.parametrize("shape", [(60, 1300), (200, 700), (97, 130)])
 def test_left_smooth_factor_across_many_row_bands(wslib, gpu_ctx, oracle, shape):
-    """The left view's raster pass runs in bands of 64 rows on separate CUs that hand their last row down through
-    device-scope words (ws_smooth.hip): tall images (up to 21 bands here), every kind of window line source
+    """The left view's raster pass runs in bands of 32 rows on separate CUs that hand their last row down through
+    device-scope words (ws_smooth.hip): tall images (up to 41 bands here), every kind of window line source
     (LDS windows with compile-time and run-time block sizes, global memory for windows without planes), a factor
     inside and one outside [0, 1], tie-heavy content."""
     w, h = shape

@@ -1,5 +1,5 @@
 """Kernel-side trouble must reach the caller as a status, not as a silently wrong map: the left view's smoothFactor
-raster pass (BlockSearch.cpp:68-73 in raster order; ws_smooth_left_bands_kernel) runs 64-row bands on separate CUs
+raster pass (BlockSearch.cpp:68-73 in raster order; ws_smooth_left_bands_kernel) runs 32-row bands on separate CUs
 that poll for the band above; a poll that never succeeds gives up after a bounded number of tries.  Round 2 set a flag
 nobody read.  WS_BAND_SPIN_LIMIT=-1 (development knob, read once per process) makes every band below the first give up
 at its first unsuccessful poll, so the path can be driven on purpose -- in a child process."""
