@@ -164,6 +164,40 @@ int ws_warp_nearest_device(ws_context *ctx, const float *src_dev, int src_w, int
                            const double m[9], float *dst_dev, int dst_w, int dst_h, int dst_stride,
                            void *stream);
 
+/* ---- rectification of an unrectified pair: the first half of ImageRectifier ------------------ */
+/*
+ * The size of a rectified image (rectification.cpp:436-483): the four corners (0,0), (w,0), (w,h), (0,h)
+ * go through H (perspectiveTransform), then cols = (int)(max_x - min_x), rows = (int)(max_y - min_y),
+ * truncated.  The rectified image is NOT translated by min_x / min_y: the reference warps with H as it is,
+ * so whatever maps left of column 0 or above row 0 is cut off -- a quirk of the reference, kept.
+ * WS_ERR_GEOMETRY if a corner has |w| <= FLT_EPSILON (perspectiveTransform would place it at (0,0)) or the
+ * size is < 1 or > 32767.  Host only: no context, no device.
+ */
+int ws_rectified_size(const double H[9], int width, int height, int *out_w, int *out_h);
+/*
+ * cv::warpPerspective(src, dst, H, Size(dst_w, dst_h)) of a CV_8UC3 image: INTER_LINEAR, BORDER_CONSTANT 0
+ * (rectification.cpp:486-493).  H is the matrix handed to warpPerspective (row-major; the call inverts it,
+ * WS_ERR_ARG if singular).  Restates OpenCV 4.x's fixed-point bilinear path (<= 4.10 on x86); later OpenCV
+ * releases may differ by one grey level.  Device pointers; dst_stride >= 3 * dst_w bytes.  Only enqueues,
+ * on `stream` (NULL = the context's own), like ws_search_device.
+ */
+int ws_rectify_device(ws_context *ctx, const ws_image *src_dev, const double H[9], uint8_t *dst_dev,
+                      int dst_w, int dst_h, int dst_stride, void *stream);
+/*
+ * ImageRectifier::rectifyImagesAndKeyPoints (image part, rectification.cpp:432-493) followed by
+ * computeDisparityMapLeft / computeDisparityMapRight (rectification.cpp:66-88), in one synchronous call:
+ * both original images go up, are rectified on the device (left with H = H_, right with Hp = Hp_, sizes from
+ * ws_rectified_size), searched as ws_search_host searches, and the rectified map is warped back with
+ * H_.inv() (INTER_NEAREST; the reference uses H_ for both views) to the original size of the left image (LEFT)
+ * or of the right image (RIGHT).  out: that many elements of out_dtype, out_stride in elements.
+ * rect_left / rect_right may be NULL; if given they receive the rectified images (getRectifiedLeft/Right,
+ * rectification.cpp:499-505), ws_rectified_size big, strides in bytes.  WS_VIEW_LINEAR is WS_ERR_ARG
+ * (ImageRectifier has no linear method); the search's checks apply to the rectified sizes.
+ */
+int ws_search_unrectified_host(ws_context *ctx, const ws_params *p, const ws_image *left, const ws_image *right,
+                               const double H[9], const double Hp[9], void *out, int out_stride, int out_dtype,
+                               uint8_t *rect_left, int rect_left_stride, uint8_t *rect_right, int rect_right_stride);
+
 /* ---- consumers of the map: the Reconstruction side of the call surface ------------------- */
 /*
  * removeDisparityOutliers(disparityMap, kernelSize, thrFront, thrBack)  (reconstruction.cpp:5-18,

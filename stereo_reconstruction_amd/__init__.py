@@ -9,6 +9,8 @@ class surface:
         .computeDisparityMapLeft(smoothFactor)                         BlockSearch.h:28
         .computeDisparityMapRight(smoothFactor, varBlock, thres)       BlockSearch.h:37
     LinearSearch(left, right).computeDisparityMap(smoothFactor)        LinearSearch.h:13-19
+    ImageRectifier(left, right, H_, Hp_)                                rectification.cpp:66-88, :432-505
+        .computeDisparityMapLeft/Right(...), .getRectifiedLeft/Right(), .getDisparityMapLeft/Right()
 
 There is no CPU fallback: if the library is missing or no HIP device answers, the calls
 raise.  The CPU oracle under oracle/ is test infrastructure and is never imported here.
@@ -22,7 +24,7 @@ import numpy as np
 
 from . import build as _build
 
-__all__ = ["WindowSearch", "BlockSearch", "LinearSearch", "WsError", "load_library",
+__all__ = ["WindowSearch", "BlockSearch", "LinearSearch", "ImageRectifier", "WsError", "load_library", "rectified_size",
            "read_pfm", "write_pfm", "read_ppm", "write_ppm", "write_mesh_off", "read_calib", "evaldisp", "VIEW_LEFT", "VIEW_RIGHT",
            "VIEW_LINEAR", "COST_SSD", "COST_SAD"]
 
@@ -41,7 +43,8 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_back_project", "ws_write_mesh_off",
            "ws_timer_begin", "ws_timer_end", "ws_set_profiling", "ws_last_kernel_ms",
            "ws_last_launch_info", "ws_last_max_block", "ws_set_tuning", "ws_set_host_bands", "ws_last_host_paths", "ws_last_wire_format", "ws_last_outliers_path", "ws_device_status",
-           "ws_pfm_read", "ws_pfm_write", "ws_free", "ws_ppm_read", "ws_ppm_write", "ws_calib_read", "ws_evaldisp"]
+           "ws_pfm_read", "ws_pfm_write", "ws_free", "ws_ppm_read", "ws_ppm_write", "ws_calib_read", "ws_evaldisp",
+           "ws_rectified_size", "ws_rectify_device", "ws_search_unrectified_host"]
 
 
 class WsError(RuntimeError):
@@ -153,6 +156,10 @@ def load_library(build_if_missing=False):
     lib.ws_calib_read.argtypes = [ctypes.c_char_p, P(_Calib)]
     lib.ws_evaldisp.argtypes = [vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_float, ci,
                                 P(ctypes.c_double)]
+    D9 = P(ctypes.c_double)
+    lib.ws_rectified_size.argtypes = [D9, ci, ci, P(ci), P(ci)]
+    lib.ws_rectify_device.argtypes = [vp, P(_Image), D9, vp, ci, ci, ci, vp]
+    lib.ws_search_unrectified_host.argtypes = [vp, P(_Params), P(_Image), P(_Image), D9, D9, vp, ci, ci, vp, ci, vp, ci]
     _lib = lib
     return lib
 
@@ -273,6 +280,43 @@ class WindowSearch:
                                                    m, out.ctypes.data, out.shape[1], out.shape[0], out.shape[1]))
         return out
 
+    # -- rectification (rectification.cpp:432-505, :66-88) ----------------------------------
+    def rectify_device(self, src_t, H, dst_t, stream=None):
+        """ws_rectify_device: cv::warpPerspective(src, dst, H, dst.size()) -- INTER_LINEAR, BORDER_CONSTANT 0 -- on
+        uint8 CUDA tensors H x W x 3 (rows may be padded: row stride >= 3 * width, pixels and channels dense).
+        Only enqueues on `stream`, a hipStream_t handle.  The default (None or 0) is the context's own stream, which is
+        NON-BLOCKING: it is not ordered against torch's null stream.  Pass the stream the tensors were written on
+        (torch.cuda.current_stream().cuda_stream when that is not the null stream) or synchronise before and after."""
+        for t in (src_t, dst_t):
+            if t.dtype != _uint8_dtype(t) or not t.is_cuda:
+                raise ValueError("expected a uint8 CUDA tensor, got %s on %s" % (t.dtype, t.device))
+            if t.dim() != 3 or t.shape[2] != 3 or t.stride(2) != 1 or t.stride(1) != 3:
+                raise ValueError("expected an H x W x 3 uint8 tensor with dense pixels")
+        Si = _Image(src_t.data_ptr(), src_t.shape[1], src_t.shape[0], src_t.stride(0))
+        self._check(self._lib.ws_rectify_device(self._h, ctypes.byref(Si), _mat9(H), dst_t.data_ptr(), dst_t.shape[1],
+                                                dst_t.shape[0], dst_t.stride(0), ctypes.c_void_p(stream or 0)))
+
+    def search_unrectified(self, params, left, right, H, Hp, dtype=np.float64, rectified=False):
+        """ws_search_unrectified_host: rectify both images on the device (left with H = H_, right with Hp = Hp_), search,
+        warp the map back with H_.inv() to the original frame.  Returns the map, or (map, rect_left, rect_right) with
+        rectified=True."""
+        La, Li = _host_image(left)
+        Ra, Ri = _host_image(right)
+        if dtype not in (np.float32, np.float64):
+            raise ValueError("dtype must be float32 or float64")
+        shape = La.shape[:2] if params.view == VIEW_LEFT else Ra.shape[:2]
+        out = np.empty(shape, dtype=dtype)
+        rl = rr = None
+        if rectified:
+            rl = np.empty(rectified_size(H, La.shape) + (3,), dtype=np.uint8)
+            rr = np.empty(rectified_size(Hp, Ra.shape) + (3,), dtype=np.uint8)
+        self._check(self._lib.ws_search_unrectified_host(
+            self._h, ctypes.byref(params), ctypes.byref(Li), ctypes.byref(Ri), _mat9(H), _mat9(Hp), out.ctypes.data,
+            shape[1], OUT_F64 if out.dtype == np.float64 else OUT_F32,
+            rl.ctypes.data if rectified else None, rl.strides[0] if rectified else 0,
+            rr.ctypes.data if rectified else None, rr.strides[0] if rectified else 0))
+        return (out, rl, rr) if rectified else out
+
     # -- consumers (Reconstruction side) ---------------------------------------------------
     def remove_disparity_outliers(self, disparity, kernel_size, thr_front, thr_back):
         m = np.array(disparity, dtype=np.float32, order="C")
@@ -379,6 +423,27 @@ def plan(params, left_shape, right_shape, num_cus=256):
     return {n: getattr(info, n) for n, _ in _PlanInfo._fields_}
 
 
+def _uint8_dtype(t):
+    import torch  # (only reached with a torch tensor in hand)
+    return torch.uint8
+
+
+def _mat9(m):
+    a = np.asarray(m, dtype=np.float64).reshape(9)
+    return (ctypes.c_double * 9)(*a)
+
+
+def rectified_size(H, shape):
+    """ws_rectified_size: (rows, cols) of the image of shape (rows, cols[, 3]) rectified with H
+    (rectification.cpp:436-483; not translated by min_x / min_y, as in the reference).  No device needed."""
+    lib = load_library()
+    w, h = ctypes.c_int(), ctypes.c_int()
+    rc = lib.ws_rectified_size(_mat9(H), int(shape[1]), int(shape[0]), ctypes.byref(w), ctypes.byref(h))
+    if rc != 0:
+        raise WsError(rc, lib.ws_last_error(None).decode())
+    return (h.value, w.value)
+
+
 _default_ctx = None
 
 
@@ -423,6 +488,46 @@ class LinearSearch:
         p = make_params(VIEW_LINEAR, 1, 0, self._range, smoothFactor, "ssd",
                         linear_range=self._range)
         return _ctx(self._context).search(p, self.leftImage, self.rightImage)
+
+
+class ImageRectifier:
+    """The boundary of the reference's ImageRectifier (rectification.hpp:50-66) once H_ and Hp_ are known: the
+    rectifying homographies come from the caller (the reference estimates them from the fundamental matrix and the
+    matches; that part is not on this path).  Rectification, search and the warp back run in one device call."""
+
+    def __init__(self, left, right, H, Hp, context=None):
+        self.leftImage_, self.rightImage_ = left, right
+        self.H_ = np.asarray(H, dtype=np.float64).reshape(3, 3)
+        self.Hp_ = np.asarray(Hp, dtype=np.float64).reshape(3, 3)
+        self._context = context
+        self.disparityMapLeft = self.disparityMapRight = None
+        self._rect = None
+
+    def _run(self, p):
+        out, rl, rr = _ctx(self._context).search_unrectified(p, self.leftImage_, self.rightImage_, self.H_, self.Hp_,
+                                                             rectified=True)
+        self._rect = (rl, rr)
+        return out
+
+    def computeDisparityMapLeft(self, blockSize, minDisparity, maxDisparity, smoothFactor):
+        self.disparityMapLeft = self._run(make_params(VIEW_LEFT, blockSize, minDisparity, maxDisparity, smoothFactor))
+
+    def computeDisparityMapRight(self, blockSize, minDisparity, maxDisparity, smoothFactor, varBlock=False, thres=10.0):
+        self.disparityMapRight = self._run(make_params(VIEW_RIGHT, blockSize, minDisparity, maxDisparity, smoothFactor,
+                                                       var_block=varBlock, thres=thres))
+
+    def getRectifiedLeft(self):
+        """The rectified left image of the last compute call (rectification.cpp:499-501)."""
+        return None if self._rect is None else self._rect[0]
+
+    def getRectifiedRight(self):
+        return None if self._rect is None else self._rect[1]
+
+    def getDisparityMapLeft(self):
+        return self.disparityMapLeft
+
+    def getDisparityMapRight(self):
+        return self.disparityMapRight
 
 
 # ---- Middlebury plumbing (no GPU needed) -------------------------------------------------

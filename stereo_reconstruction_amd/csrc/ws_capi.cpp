@@ -4,7 +4,9 @@
 // plumbing (PFM, calib.txt, evaldisp).  Compiled with hipcc; no compute happens on the host.
 #include "../../include/ws_stereo.h"
 #include "ws_kernels.h"
+#include "ws_rectify.h"
 
+#include <float.h>
 #include <math.h>
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -519,6 +521,7 @@ struct ws_context {
     bool scratch_busy = false;
     bool profiling = false, kernel_timed = false;
     DevBuf plane_a, plane_b, keys, cost, bs_plane, max_block, sel, sel_planes, top3, d_left, d_right, d_out, d_out64 /* the consumers' scratch */, d_out16;
+    DevBuf d_rect_left, d_rect_right; // ws_search_unrectified_host: the rectified images
     Job jobs[2];             // ws_enqueue_host alternates between two slots
     int job_next = 0;
     hipStream_t copy_stream = nullptr; // host <-> device copies of the batched path, beside the searches
@@ -1038,7 +1041,8 @@ void ws_destroy(ws_context *ctx)
     // abandoned the batch may have freed the buffers the staged maps would be written to
     for (HostSpan &b : ctx->batch_spans) b.down.clear();
     ctx->batch_spans.clear();
-    for (DevBuf *b : {&ctx->plane_a, &ctx->plane_b, &ctx->keys, &ctx->cost, &ctx->bs_plane, &ctx->max_block, &ctx->sel, &ctx->sel_planes, &ctx->top3, &ctx->d_left, &ctx->d_right, &ctx->d_out, &ctx->d_out64, &ctx->d_out16, &ctx->d_flag})
+    for (DevBuf *b : {&ctx->plane_a, &ctx->plane_b, &ctx->keys, &ctx->cost, &ctx->bs_plane, &ctx->max_block, &ctx->sel, &ctx->sel_planes, &ctx->top3, &ctx->d_left, &ctx->d_right, &ctx->d_out, &ctx->d_out64, &ctx->d_out16, &ctx->d_flag,
+                    &ctx->d_rect_left, &ctx->d_rect_right})
         if (b->p) (void)hipFree(b->p);
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
     for (HostBuf *b : {&ctx->h_left, &ctx->h_right, &ctx->h_out, &ctx->h_aux[0], &ctx->h_aux[1], &ctx->jobs[0].h_left, &ctx->jobs[0].h_right,
@@ -1503,6 +1507,129 @@ int ws_warp_nearest_host(ws_context *ctx, const double *src, int src_w, int src_
     for (int y = 0; y < dst_h; ++y)
         for (int x = 0; x < dst_w; ++x) dst[(size_t)y * dst_stride + x] = (double)hd[(size_t)y * dst_w + x];
     return WS_OK;
+}
+
+// ---- rectification (src/Rectification/rectification.cpp) ------------------------------
+
+// rectification.cpp:436-483: perspectiveTransform of the four corners (x' = (x*m0 + y*m1 + m2) * (1/w),
+// w = x*m6 + y*m7 + m8), then the extent truncated to int.  perspectiveTransform puts a corner with |w| <= FLT_EPSILON
+// at (0,0); such a homography sends the image to infinity and is refused instead.
+int ws_rectified_size(const double H[9], int width, int height, int *out_w, int *out_h)
+{
+    if (!H || !out_w || !out_h || width <= 0 || height <= 0) return fail(nullptr, WS_ERR_ARG, "bad rectified-size arguments");
+    const double cx[4] = {0.0, (double)width, (double)width, 0.0}, cy[4] = {0.0, 0.0, (double)height, (double)height};
+    double min_x = INFINITY, min_y = INFINITY, max_x = -INFINITY, max_y = -INFINITY;
+    for (int j = 0; j < 4; ++j) {
+        double w = cx[j] * H[6] + cy[j] * H[7] + H[8];
+        if (!(fabs(w) > FLT_EPSILON)) return fail(nullptr, WS_ERR_GEOMETRY, "corner %d maps to infinity (|w| <= FLT_EPSILON)", j);
+        w = 1.0 / w;
+        const double X = (cx[j] * H[0] + cy[j] * H[1] + H[2]) * w, Y = (cx[j] * H[3] + cy[j] * H[4] + H[5]) * w;
+        min_x = std::min(X, min_x); max_x = std::max(X, max_x);
+        min_y = std::min(Y, min_y); max_y = std::max(Y, max_y);
+    }
+    const double cols = max_x - min_x, rows = max_y - min_y;
+    // (int) truncates: a size in [1, 32767] is an extent in [1, 32768)
+    if (!(cols >= 1.0 && cols < 32768.0 && rows >= 1.0 && rows < 32768.0))
+        return fail(nullptr, WS_ERR_GEOMETRY, "rectified size %g x %g outside [1, 32767]", cols, rows);
+    *out_w = (int)cols;
+    *out_h = (int)rows;
+    return WS_OK;
+}
+
+int ws_rectify_device(ws_context *ctx, const ws_image *src_dev, const double H[9], uint8_t *dst_dev, int dst_w, int dst_h,
+                      int dst_stride, void *stream)
+{
+    if (!ctx) return WS_ERR_ARG;
+    if (!image_ok(src_dev) || !H || !dst_dev || dst_w <= 0 || dst_h <= 0 || (long long)dst_stride < 3LL * dst_w)
+        return fail(ctx, WS_ERR_ARG, "bad rectify arguments");
+    double inv[9];
+    if (!invert3x3(H, inv)) return fail(ctx, WS_ERR_ARG, "singular warp matrix");
+    WS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    WS_HIP(ctx, launch_rectify(src_dev->data, src_dev->width, src_dev->height, src_dev->stride, inv, dst_dev, dst_w, dst_h,
+                               dst_stride, s));
+    return WS_OK;
+}
+
+// ImageRectifier: rectifyImagesAndKeyPoints (images) + computeDisparityMapLeft/Right, on the context stream: the
+// originals go up as in ws_search_host, both are rectified into context scratch, searched by the same device path, the
+// rectified map is warped back with H_.inv() (nearest) and comes down as float32, widened to the caller's type on the
+// host.  One synchronisation at the end.
+int ws_search_unrectified_host(ws_context *ctx, const ws_params *p, const ws_image *left, const ws_image *right,
+                               const double H[9], const double Hp[9], void *out, int out_stride, int out_dtype,
+                               uint8_t *rect_left, int rect_left_stride, uint8_t *rect_right, int rect_right_stride)
+{
+    if (!ctx) return WS_ERR_ARG;
+    if (!p || !image_ok(left) || !image_ok(right) || !H || !Hp) return fail(ctx, WS_ERR_ARG, "null or malformed image / params / homography");
+    if (p->view == WS_VIEW_LINEAR) return fail(ctx, WS_ERR_ARG, "ImageRectifier has no LinearSearch method");
+    if (!out || (out_dtype != WS_OUT_F32 && out_dtype != WS_OUT_F64)) return fail(ctx, WS_ERR_ARG, "bad output");
+    double h_inv[9], hp_inv[9], back[9]; // M^-1 of the two forward warps; M^-1 of the warp back, M = H_.inv()
+    if (!invert3x3(H, h_inv) || !invert3x3(Hp, hp_inv) || !invert3x3(h_inv, back)) return fail(ctx, WS_ERR_ARG, "singular homography");
+    int lw, lh, rw, rh, rc;
+    if ((rc = ws_rectified_size(H, left->width, left->height, &lw, &lh)) != WS_OK ||
+        (rc = ws_rectified_size(Hp, right->width, right->height, &rw, &rh)) != WS_OK)
+        return fail(ctx, rc, "%s", ws_last_error(nullptr));
+    const ws_image shape_l{left->data, lw, lh, 3 * lw}, shape_r{right->data, rw, rh, 3 * rw};
+    if ((rc = check_params(ctx, p, &shape_l, &shape_r)) != WS_OK) return rc;
+    const bool lv = p->view == WS_VIEW_LEFT;
+    const int ow = lv ? left->width : right->width, oh = lv ? left->height : right->height; // the original frame
+    const int mw = lv ? lw : rw, mh = lv ? lh : rh;                                         // the rectified map
+    if (out_stride < ow) return fail(ctx, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
+    if ((rect_left && rect_left_stride < 3 * lw) || (rect_right && rect_right_stride < 3 * rw))
+        return fail(ctx, WS_ERR_ARG, "rectified image stride below 3 * width");
+    WS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t lb = (size_t)left->width * 3, rb = (size_t)right->width * 3;
+    const bool lin_l = linear_span(left), lin_r = linear_span(right);
+    const size_t span_l = lin_l ? (size_t)left->stride * (left->height - 1) + lb : lb * left->height;
+    const size_t span_r = lin_r ? (size_t)right->stride * (right->height - 1) + rb : rb * right->height;
+    if ((rc = ensure(ctx, ctx->d_left, span_l)) != WS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->d_right, span_r)) != WS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->d_rect_left, (size_t)lw * lh * 3)) != WS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->d_rect_right, (size_t)rw * rh * 3)) != WS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->d_out, (size_t)mw * mh * 4)) != WS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->d_out64, (size_t)ow * oh * 4)) != WS_OK) return rc;
+    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    // the caller's buffers for the duration of the call (HostSpan, like ws_search_host)
+    HostSpan sp[5];
+    if (lin_l) { sp[0].p = const_cast<uint8_t *>(left->data); sp[0].n = span_l; sp[0].stage = &ctx->h_left; }
+    if (lin_r) { sp[1].p = const_cast<uint8_t *>(right->data); sp[1].n = span_r; sp[1].stage = &ctx->h_right; }
+    sp[2].p = static_cast<uint8_t *>(out); sp[2].n = ((size_t)out_stride * (oh - 1) + ow) * esz; sp[2].stage = &ctx->h_out;
+    if (rect_left) { sp[3].p = rect_left; sp[3].n = (size_t)rect_left_stride * (lh - 1) + 3 * (size_t)lw; sp[3].stage = &ctx->h_aux[0]; }
+    if (rect_right) { sp[4].p = rect_right; sp[4].n = (size_t)rect_right_stride * (rh - 1) + 3 * (size_t)rw; sp[4].stage = &ctx->h_aux[1]; }
+    spans_attach(sp, 5);
+    uint8_t *drl = static_cast<uint8_t *>(ctx->d_rect_left.p), *drr = static_cast<uint8_t *>(ctx->d_rect_right.p);
+    rc = [&]() -> int {
+        if (!lin_l) WS_HIP(ctx, gather_rows(ctx->h_left, left));
+        if (!lin_r) WS_HIP(ctx, gather_rows(ctx->h_right, right));
+        if (lin_l) WS_HIP(ctx, span_upload(sp[0], 0, ctx->d_left.p, span_l, s));
+        else WS_HIP(ctx, hipMemcpyAsync(ctx->d_left.p, ctx->h_left.p, span_l, hipMemcpyHostToDevice, s));
+        if (lin_r) WS_HIP(ctx, span_upload(sp[1], 0, ctx->d_right.p, span_r, s));
+        else WS_HIP(ctx, hipMemcpyAsync(ctx->d_right.p, ctx->h_right.p, span_r, hipMemcpyHostToDevice, s));
+        // warpPerspective(leftImage_, .., H_, size), warpPerspective(rightImage_, .., Hp_, size) (rectification.cpp:486-493)
+        WS_HIP(ctx, launch_rectify(static_cast<const uint8_t *>(ctx->d_left.p), left->width, left->height, lin_l ? left->stride : (int)lb,
+                                   h_inv, drl, lw, lh, 3 * lw, s));
+        WS_HIP(ctx, launch_rectify(static_cast<const uint8_t *>(ctx->d_right.p), right->width, right->height, lin_r ? right->stride : (int)rb,
+                                   hp_inv, drr, rw, rh, 3 * rw, s));
+        // BlockSearch on the rectified pair (rectification.cpp:67-68, :79-80)
+        const ws_image il{drl, lw, lh, 3 * lw}, ir{drr, rw, rh, 3 * rw};
+        float *rect_map = static_cast<float *>(ctx->d_out.p), *map = static_cast<float *>(ctx->d_out64.p);
+        int rc2;
+        if ((rc2 = run_device_wire(ctx, p, &il, &ir, rect_map, nullptr, kWireF32, mw, s)) != WS_OK) return rc2;
+        // cv::warpPerspective(disparityMap_rect, .., H_.inv(), original size, INTER_NEAREST) (rectification.cpp:70-75, :82-87)
+        WS_HIP(ctx, launch_warp(rect_map, mw, mh, mw, map, ow, oh, ow, back, s));
+        WS_HIP(ctx, span_download(sp[2], 0, (size_t)out_stride, map, (size_t)ow, (size_t)oh, kWireF32, esz, s));
+        if (rect_left) WS_HIP(ctx, span_download_bytes(sp[3], 0, (size_t)rect_left_stride, drl, 3 * (size_t)lw, (size_t)lh, s));
+        if (rect_right) WS_HIP(ctx, span_download_bytes(sp[4], 0, (size_t)rect_right_stride, drr, 3 * (size_t)rw, (size_t)rh, s));
+        return WS_OK;
+    }();
+    // (also after an error: nothing may still be copying when the ranges are released)
+    const hipError_t es = hipStreamSynchronize(s);
+    if (rc != WS_OK || es != hipSuccess) // (nothing half-done reaches the caller)
+        for (HostSpan &h : sp) h.down.clear();
+    spans_finish(sp, 5);
+    if (rc == WS_OK && es != hipSuccess) return fail(ctx, WS_ERR_HIP, "unrectified host call: %s", hipGetErrorString(es));
+    return rc == WS_OK ? check_device_status(ctx) : rc;
 }
 
 // ---- consumers of the map (src/Reconstruction/reconstruction.cpp) ----------------------

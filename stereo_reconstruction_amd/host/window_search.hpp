@@ -9,6 +9,9 @@
 //       auto bs  = wsamd::BlockSearch(wsamd::view(left), wsamd::view(right), blockSize, minD, maxD);
 //       wsamd::MatF64 d = bs.computeDisparityMapLeft(smoothFactor);      // doubles, row-major
 //
+// An unrectified pair goes through ImageRectifier (rectification.cpp:66-88, :432-505): the image warps, the search
+// and the warp back in one device call.
+//
 // Header only; link against libws_stereo.so.  Errors the reference raises as cv::Exception
 // (even blockSize, ROI outside the image) and everything the device cannot run surface as
 // wsamd::Error.  Define WSAMD_WITH_OPENCV before including to get cv::Mat adapters.
@@ -238,6 +241,97 @@ private:
     double H_[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     int rows_[2] = {0, 0}, cols_[2] = {0, 0};
     bool warp_ = false;
+    MatF64 disparityMapLeft, disparityMapRight;
+};
+
+// A CV_8UC3 image owned by value (what ImageRectifier::getRectifiedLeft/Right return, rectification.cpp:499-505).
+class Mat8UC3 {
+public:
+    Mat8UC3() = default;
+    Mat8UC3(int rows, int cols) : rows(rows), cols(cols), buf_(static_cast<size_t>(rows) * cols * 3, 0) {}
+    int rows = 0, cols = 0;
+    size_t step() const { return static_cast<size_t>(cols) * 3; }
+    uint8_t *ptr() { return buf_.data(); }
+    const uint8_t *ptr() const { return buf_.data(); }
+    bool empty() const { return buf_.empty(); }
+    Image8UC3 view() const { return wsamd::view(buf_.data(), rows, cols); }
+
+private:
+    std::vector<uint8_t> buf_;
+};
+
+// ImageRectifier (rectification.hpp:50-66) from the point where H_ and Hp_ are known: built from the ORIGINAL pair
+// and the two rectifying homographies (the reference estimates them from F and the matches; not on this path).
+// Each compute call is one ws_search_unrectified_host: both images rectified on the device
+// (warpPerspective(.., H_ / Hp_, size), rectification.cpp:486-493, sizes from ws_rectified_size), the block search,
+// and the warp back with H_.inv() to the original size (rectification.cpp:66-88).  The rectified images of the last
+// compute call are kept for getRectifiedLeft/Right.  For pairs that are already rectified use RectifiedPair.
+class ImageRectifier {
+public:
+    ImageRectifier(const Image8UC3 &leftImage, const Image8UC3 &rightImage, const double H[9], const double Hp[9],
+                   Device &device = Device::shared())
+        : leftImage_(leftImage), rightImage_(rightImage), device_(device)
+    {
+        for (int i = 0; i < 9; ++i) { H_[i] = H[i]; Hp_[i] = Hp[i]; }
+        int w, h;
+        int rc = ws_rectified_size(H_, leftImage.cols, leftImage.rows, &w, &h);
+        if (rc != WS_OK) throw Error(rc, ws_last_error(nullptr));
+        leftRectifiedImage_ = Mat8UC3(h, w);
+        rc = ws_rectified_size(Hp_, rightImage.cols, rightImage.rows, &w, &h);
+        if (rc != WS_OK) throw Error(rc, ws_last_error(nullptr));
+        rightRectifiedImage_ = Mat8UC3(h, w);
+    }
+    void computeDisparityMapLeft(int blockSize, int minDisparity, int maxDisparity, double smoothFactor)
+    {
+        disparityMapLeft = run(params(WS_VIEW_LEFT, blockSize, minDisparity, maxDisparity, smoothFactor), leftImage_);
+    }
+    void computeDisparityMapRight(int blockSize, int minDisparity, int maxDisparity, double smoothFactor,
+                                  bool varBlock = false, double thres = 10.0) // default thres: rectification.hpp:66
+    {
+        ws_params p = params(WS_VIEW_RIGHT, blockSize, minDisparity, maxDisparity, smoothFactor);
+        p.var_block = varBlock;
+        p.thres = thres;
+        disparityMapRight = run(p, rightImage_);
+    }
+    // full size from construction on (ws_rectified_size), all zeros until the first compute call fills them
+    const Mat8UC3 &getRectifiedLeft() const { return leftRectifiedImage_; }
+    const Mat8UC3 &getRectifiedRight() const { return rightRectifiedImage_; }
+    const MatF64 &getDisparityMapLeft() const { return disparityMapLeft; }
+    const MatF64 &getDisparityMapRight() const { return disparityMapRight; }
+    const double *getH_() const { return H_; }
+    const double *getHp_() const { return Hp_; }
+
+    int cost = WS_COST_SSD; // the build's extensions, as on BlockSearch
+    bool subpixel = false;
+
+private:
+    ws_params params(int view, int blockSize, int minDisparity, int maxDisparity, double smoothFactor) const
+    {
+        ws_params p;
+        ws_params_default(&p);
+        p.view = view;
+        p.cost = cost;
+        p.block_size = blockSize;
+        p.min_disparity = minDisparity;
+        p.max_disparity = maxDisparity;
+        p.smooth_factor = smoothFactor;
+        p.subpixel = subpixel;
+        return p;
+    }
+    MatF64 run(const ws_params &p, const Image8UC3 &frame) // the map comes back in the original frame of `frame`
+    {
+        MatF64 out(frame.rows, frame.cols);
+        const ws_image li = detail::to_c(leftImage_), ri = detail::to_c(rightImage_);
+        const int rc = ws_search_unrectified_host(device_.get(), &p, &li, &ri, H_, Hp_, out.ptr(), out.cols, WS_OUT_F64,
+                                                  leftRectifiedImage_.ptr(), static_cast<int>(leftRectifiedImage_.step()),
+                                                  rightRectifiedImage_.ptr(), static_cast<int>(rightRectifiedImage_.step()));
+        if (rc != WS_OK) throw Error(rc, ws_last_error(device_.get()));
+        return out;
+    }
+    Image8UC3 leftImage_, rightImage_;
+    Device &device_;
+    double H_[9], Hp_[9];
+    Mat8UC3 leftRectifiedImage_, rightRectifiedImage_;
     MatF64 disparityMapLeft, disparityMapRight;
 };
 
