@@ -198,6 +198,58 @@ int ws_search_unrectified_host(ws_context *ctx, const ws_params *p, const ws_ima
                                const double H[9], const double Hp[9], void *out, int out_stride, int out_dtype,
                                uint8_t *rect_left, int rect_left_stride, uint8_t *rect_right, int rect_right_stride);
 
+/* ---- many pairs over the devices of a node ------------------------------------------------ */
+/*
+ * Independent pairs are dealt to WORKERS: one ws_context and one host thread each.  Workers are device indices; a device
+ * may repeat (several contexts then share it).  Each worker runs its items as ws_enqueue_host runs pairs (two in
+ * flight on its context) and ends with ws_wait.  Every map is bit-identical to ws_search_host of that pair on one
+ * context, for both out_dtypes and both wire formats.  The assignment restates stereo_reconstruction_amd/sharding.py:
+ *   whole pairs (bands == 0, or a batch that cannot be banded): lpt_assign, cost out_w * out_h * nd with
+ *     nd = max_disparity (LEFT), max_disparity - min_disparity (RIGHT), linear_range (LINEAR);
+ *   row bands (bands == 1): band_items, if every job is LEFT or RIGHT with smoothFactor 1, no varBlock, equal image
+ *     heights, and all jobs share block_size and nd (>= 1).  A band is the search of the sub-images
+ *     [max(0, y0 - half), min(h, y1 + half)); only its map rows [y0, y1) are written to `out`.
+ */
+#define WS_JOB_NOT_RUN 1 /* ws_job.status: its worker stopped at an earlier error (or another job was invalid) */
+
+typedef struct ws_batch ws_batch; /* not to be shared between threads (like ws_context); not usable in a forked child */
+
+typedef struct { /* one pair: what ws_enqueue_host takes, plus its outcome */
+    ws_params params;
+    ws_image left, right; /* host buffers */
+    void *out;            /* the map: out_h x out_w elements of out_dtype, out_stride elements apart */
+    int out_stride;
+    int out_dtype;
+    int status; /* out: WS_OK, a WS_ERR_*, or WS_JOB_NOT_RUN */
+} ws_job;
+
+typedef struct { int job, y0, y1, worker; } ws_batch_item; /* map rows [y0, y1) of job `job`, searched on worker `worker` */
+
+/*
+ * devices: n_workers device indices (a device may repeat); NULL = one worker per device of ws_device_count() (n_workers
+ * is then ignored).  Creates the workers' contexts.  Message of a failure via ws_batch_last_error(NULL).
+ */
+int ws_batch_create(const int *devices, int n_workers, ws_batch **out);
+void ws_batch_destroy(ws_batch *b);
+/* Text of the last error of this batch (b == NULL: of the last failed ws_batch_create / ws_batch_plan on this thread). */
+const char *ws_batch_last_error(const ws_batch *b);
+int ws_batch_workers(const ws_batch *b, int *devices, int cap); /* the workers' devices; returns their count */
+/*
+ * Host only, no device: the items a batch call with n_workers workers would run, grouped by worker.  Checks the jobs'
+ * parameters and images as ws_validate does (not their `out`).  *n_items = the number of items (at most
+ * n_jobs + n_workers - 1); WS_ERR_ARG if that exceeds cap.  *banded = 1 if the batch was cut into row bands.
+ */
+int ws_batch_plan(const ws_job *jobs, int n_jobs, int n_workers, int bands, int min_rows, ws_batch_item *items, int cap,
+                  int *n_items, int *banded);
+/*
+ * Synchronous: every map is in its `out` on return.  Every job is checked first, with the checks of ws_enqueue_host; if
+ * any is invalid, nothing is searched, no `out` is written, the call returns the status of the lowest-index invalid job
+ * and the message names it.  A worker that meets an error stops: its remaining items are not run, the other workers
+ * finish theirs.  Each job's status is set; the call returns the error of the lowest-index job that has one.
+ * bands: 0 = whole pairs, 1 = row bands where the batch allows them; min_rows >= 1 (bands keep at least that many rows).
+ */
+int ws_batch_search_host(ws_batch *b, ws_job *jobs, int n_jobs, int bands, int min_rows);
+
 /* ---- consumers of the map: the Reconstruction side of the call surface ------------------- */
 /*
  * removeDisparityOutliers(disparityMap, kernelSize, thrFront, thrBack)  (reconstruction.cpp:5-18,

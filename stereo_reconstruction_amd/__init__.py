@@ -24,7 +24,7 @@ import numpy as np
 
 from . import build as _build
 
-__all__ = ["WindowSearch", "BlockSearch", "LinearSearch", "ImageRectifier", "WsError", "load_library", "rectified_size",
+__all__ = ["WindowSearch", "BatchSearch", "BlockSearch", "LinearSearch", "ImageRectifier", "WsError", "load_library", "rectified_size",
            "read_pfm", "write_pfm", "read_ppm", "write_ppm", "write_mesh_off", "read_calib", "evaldisp", "VIEW_LEFT", "VIEW_RIGHT",
            "VIEW_LINEAR", "COST_SSD", "COST_SAD"]
 
@@ -44,7 +44,10 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_timer_begin", "ws_timer_end", "ws_set_profiling", "ws_last_kernel_ms",
            "ws_last_launch_info", "ws_last_max_block", "ws_set_tuning", "ws_set_host_bands", "ws_last_host_paths", "ws_last_wire_format", "ws_last_outliers_path", "ws_device_status",
            "ws_pfm_read", "ws_pfm_write", "ws_free", "ws_ppm_read", "ws_ppm_write", "ws_calib_read", "ws_evaldisp",
-           "ws_rectified_size", "ws_rectify_device", "ws_search_unrectified_host"]
+           "ws_rectified_size", "ws_rectify_device", "ws_search_unrectified_host",
+           "ws_batch_create", "ws_batch_destroy", "ws_batch_last_error", "ws_batch_workers", "ws_batch_plan",
+           "ws_batch_search_host"]
+JOB_NOT_RUN = 1  # ws_job.status of a job its worker never reached (WS_JOB_NOT_RUN)
 
 
 class WsError(RuntimeError):
@@ -64,6 +67,15 @@ class _Params(ctypes.Structure):
                 ("smooth_factor", ctypes.c_double), ("var_block", ctypes.c_int),
                 ("thres", ctypes.c_double), ("subpixel", ctypes.c_int),
                 ("linear_range", ctypes.c_int)]
+
+
+class _Job(ctypes.Structure):
+    _fields_ = [("params", _Params), ("left", _Image), ("right", _Image), ("out", ctypes.c_void_p),
+                ("out_stride", ctypes.c_int), ("out_dtype", ctypes.c_int), ("status", ctypes.c_int)]
+
+
+class _BatchItem(ctypes.Structure):
+    _fields_ = [("job", ctypes.c_int), ("y0", ctypes.c_int), ("y1", ctypes.c_int), ("worker", ctypes.c_int)]
 
 
 class _Calib(ctypes.Structure):
@@ -160,6 +172,14 @@ def load_library(build_if_missing=False):
     lib.ws_rectified_size.argtypes = [D9, ci, ci, P(ci), P(ci)]
     lib.ws_rectify_device.argtypes = [vp, P(_Image), D9, vp, ci, ci, ci, vp]
     lib.ws_search_unrectified_host.argtypes = [vp, P(_Params), P(_Image), P(_Image), D9, D9, vp, ci, ci, vp, ci, vp, ci]
+    lib.ws_batch_create.argtypes = [P(ci), ci, P(vp)]
+    lib.ws_batch_destroy.argtypes = [vp]
+    lib.ws_batch_destroy.restype = None
+    lib.ws_batch_last_error.argtypes = [vp]
+    lib.ws_batch_last_error.restype = ctypes.c_char_p
+    lib.ws_batch_workers.argtypes = [vp, P(ci), ci]
+    lib.ws_batch_plan.argtypes = [P(_Job), ci, ci, ci, ci, P(_BatchItem), ci, P(ci), P(ci)]
+    lib.ws_batch_search_host.argtypes = [vp, P(_Job), ci, ci, ci]
     _lib = lib
     return lib
 
@@ -398,6 +418,102 @@ class WindowSearch:
 
     def set_tuning(self, x_runs_per_tile=0, strip_rows=0, threads=0):
         self._check(self._lib.ws_set_tuning(self._h, x_runs_per_tile, strip_rows, threads))
+
+
+def _param_list(params_or_list, n):
+    if isinstance(params_or_list, (list, tuple)):
+        if len(params_or_list) != n:
+            raise ValueError("%d parameter sets for %d pairs" % (len(params_or_list), n))
+        return list(params_or_list)
+    return [params_or_list] * n
+
+
+def batch_plan(params_or_list, shapes, n_workers, bands=True, min_rows=256):
+    """ws_batch_plan: the items a BatchSearch of n_workers workers would run on pairs of these shapes, without a device.
+    shapes: per pair ((left rows, cols), (right rows, cols)), or one (rows, cols) for both images.  Returns
+    (items, banded): items = [(job, y0, y1, worker)] grouped by worker -- map rows [y0, y1) of pair `job` --, banded =
+    whether the batch was cut into row bands (sharding.band_items) rather than dealt as whole pairs (sharding.lpt_assign)."""
+    shapes = [s if isinstance(s[0], (tuple, list)) else (s, s) for s in shapes]
+    plist = _param_list(params_or_list, len(shapes))
+    jobs = (_Job * max(1, len(shapes)))()
+    for k, ((ls, rs), p) in enumerate(zip(shapes, plist)):
+        jobs[k].params, jobs[k].left, jobs[k].right = p, _shape_image(ls), _shape_image(rs)
+    cap = len(shapes) + max(1, n_workers)
+    items = (_BatchItem * cap)()
+    n, banded = ctypes.c_int(), ctypes.c_int()
+    lib = load_library()
+    rc = lib.ws_batch_plan(jobs, len(shapes), n_workers, int(bool(bands)), min_rows, items, cap, ctypes.byref(n),
+                           ctypes.byref(banded))
+    if rc != 0:
+        raise WsError(rc, lib.ws_batch_last_error(None).decode())
+    return [(it.job, it.y0, it.y1, it.worker) for it in items[:n.value]], bool(banded.value)
+
+
+class BatchSearch:
+    """Many independent pairs over several devices (ws_batch_*): one worker -- a context and a host thread -- per entry
+    of `devices` (a device may repeat; None = one per device of the node).  Pairs are dealt as whole pairs (LPT) or as
+    row bands (sharding.band_items); every map equals WindowSearch.search of that pair."""
+
+    def __init__(self, devices=None):
+        self._lib = load_library()
+        h = ctypes.c_void_p()
+        if devices is None:
+            rc = self._lib.ws_batch_create(None, 0, ctypes.byref(h))
+        else:
+            devices = [int(d) for d in devices]
+            arr = (ctypes.c_int * max(1, len(devices)))(*devices)
+            rc = self._lib.ws_batch_create(arr, len(devices), ctypes.byref(h))
+        if rc != 0:
+            raise WsError(rc, self._lib.ws_batch_last_error(None).decode())
+        self._h = h
+        n = self._lib.ws_batch_workers(self._h, None, 0)
+        arr = (ctypes.c_int * max(1, n))()
+        self._lib.ws_batch_workers(self._h, arr, n)
+        self.workers = list(arr[:n])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ws_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def plan(self, params_or_list, pairs, bands=True, min_rows=256):
+        """What search() would run on these pairs (image arrays or shapes): ([(job, y0, y1, worker)], banded)."""
+        shapes = [p if isinstance(p[0], (tuple, list)) else (p[0].shape[:2], p[1].shape[:2]) for p in pairs]
+        return batch_plan(params_or_list, shapes, len(self.workers), bands, min_rows)
+
+    def search(self, params_or_list, pairs, dtype=np.float32, bands=True, min_rows=256, outs=None):
+        """ws_batch_search_host: the maps of all pairs (one params for all, or one per pair).  `outs`: C-contiguous
+        float32 / float64 arrays of the maps' shapes to write into instead of fresh ones.  Raises WsError with the first
+        failed job's status; every array stays alive until the call has returned."""
+        plist = _param_list(params_or_list, len(pairs))
+        jobs = (_Job * max(1, len(pairs)))()
+        keep, maps = [], []
+        for k, ((left, right), p) in enumerate(zip(pairs, plist)):
+            La, Li = _host_image(left)
+            Ra, Ri = _host_image(right)
+            shape = La.shape[:2] if p.view == VIEW_LEFT else Ra.shape[:2]
+            out = np.empty(shape, dtype=dtype) if outs is None else outs[k]
+            if out.shape != shape or not out.flags["C_CONTIGUOUS"] or out.dtype not in (np.float32, np.float64):
+                raise ValueError("out %d must be a C-contiguous float32 / float64 array of shape %s" % (k, shape))
+            keep.append((La, Ra))
+            maps.append(out)
+            jobs[k].params, jobs[k].left, jobs[k].right = p, Li, Ri
+            jobs[k].out, jobs[k].out_stride = out.ctypes.data, shape[1]
+            jobs[k].out_dtype = OUT_F64 if out.dtype == np.float64 else OUT_F32
+        rc = self._lib.ws_batch_search_host(self._h, jobs, len(pairs), int(bool(bands)), min_rows)
+        self.statuses = [jobs[k].status for k in range(len(pairs))]
+        del keep
+        if rc != 0:
+            raise WsError(rc, self._lib.ws_batch_last_error(self._h).decode())
+        return maps
 
 
 def _shape_image(shape):

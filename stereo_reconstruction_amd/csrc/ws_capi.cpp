@@ -5,6 +5,7 @@
 #include "../../include/ws_stereo.h"
 #include "ws_kernels.h"
 #include "ws_rectify.h"
+#include "ws_capi_internal.h"
 
 #include <float.h>
 #include <math.h>
@@ -51,6 +52,7 @@ struct Job { // one pair in flight on the batched host path
     hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
     void *user_out = nullptr;
     int w = 0, h = 0, out_stride = 0, dtype = 0;
+    int row0 = 0;         // the first row of the device map that goes to user_out (a row band: its halo rows stay behind)
     bool pending = false; // searched (or being searched), result not yet on its way to user_out
     HostBuf h_left, h_right; // gathered rows of images that do not cross as one span (gather_rows), or their stage
     HostBuf h_out;           // stage of a pageable map (HostSpan)
@@ -1336,7 +1338,8 @@ static int flush_job(ws_context *ctx, Job &j)
     j.pending = false;
     WS_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, j.ev_done, 0));
     const int esz = j.dtype == WS_OUT_F32 ? 4 : 8;
-    const void *src = j.wire == kWireI16 ? static_cast<const void *>(j.d_out16) : static_cast<const void *>(j.d_out);
+    const size_t first = (size_t)j.row0 * j.w;
+    const void *src = j.wire == kWireI16 ? static_cast<const void *>(j.d_out16 + first) : static_cast<const void *>(j.d_out + first);
     WS_HIP(ctx, span_download(ctx->batch_spans[(size_t)j.out_span], 0, (size_t)j.out_stride, src, (size_t)j.w, (size_t)j.h, j.wire, esz,
                               ctx->copy_stream));
     return WS_OK;
@@ -1345,6 +1348,17 @@ static int flush_job(ws_context *ctx, Job &j)
 int ws_enqueue_host(ws_context *ctx, const ws_params *p, const ws_image *left, const ws_image *right,
                     void *out, int out_stride, int out_dtype)
 {
+    return wsamd::enqueue_host_rows(ctx, p, left, right, out, out_stride, out_dtype, 0, -1);
+}
+
+} // extern "C"
+
+// ws_enqueue_host of the rows [map_row0, map_row0 + map_rows) of the pair's map only (map_rows < 0: all of them):
+// `out` is where map row map_row0 lands.  A row band of a bigger pair (ws_batch_search_host) is the search of its
+// sub-images, halo rows included; only the band's own rows come down, so neighbouring bands never write each other's.
+int wsamd::enqueue_host_rows(ws_context *ctx, const ws_params *p, const ws_image *left, const ws_image *right, void *out,
+                             int out_stride, int out_dtype, int map_row0, int map_rows)
+{
     if (!ctx) return WS_ERR_ARG;
     int rc = check_params(ctx, p, left, right);
     if (rc != WS_OK) return rc;
@@ -1352,6 +1366,12 @@ int ws_enqueue_host(ws_context *ctx, const ws_params *p, const ws_image *left, c
     int ow, oh;
     out_dims(p, left, right, &ow, &oh);
     if (out_stride < ow) return fail(ctx, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
+    if (map_rows < 0) {
+        map_row0 = 0;
+        map_rows = oh;
+    }
+    if (map_row0 < 0 || map_rows < 1 || map_row0 + map_rows > oh)
+        return fail(ctx, WS_ERR_ARG, "map rows [%d, %d) outside [0, %d)", map_row0, map_row0 + map_rows, oh);
     WS_HIP(ctx, hipSetDevice(ctx->device));
     Job &job = ctx->jobs[ctx->job_next];
     Job &prev = ctx->jobs[ctx->job_next ^ 1];
@@ -1393,7 +1413,7 @@ int ws_enqueue_host(ws_context *ctx, const ws_params *p, const ws_image *left, c
     HostSpan sp[3];
     if (lin_l) { sp[0].p = const_cast<uint8_t *>(left->data); sp[0].n = span_l; sp[0].stage = &job.h_left; }
     if (lin_r) { sp[1].p = const_cast<uint8_t *>(right->data); sp[1].n = span_r; sp[1].stage = &job.h_right; }
-    sp[2].p = static_cast<uint8_t *>(out); sp[2].n = ((size_t)out_stride * (oh - 1) + ow) * esz; sp[2].stage = &job.h_out;
+    sp[2].p = static_cast<uint8_t *>(out); sp[2].n = ((size_t)out_stride * (map_rows - 1) + ow) * esz; sp[2].stage = &job.h_out;
     spans_attach(sp, 3);
     const size_t first = ctx->batch_spans.size();
     for (int i = 0; i < 3; ++i) ctx->batch_spans.push_back(sp[i]);
@@ -1418,12 +1438,14 @@ int ws_enqueue_host(ws_context *ctx, const ws_params *p, const ws_image *left, c
     job.wire = wire_for(p, left, right);
     if ((rc = run_device_wire(ctx, p, &dl, &dr, job.d_out, job.d_out16, job.wire, ow, ctx->stream)) != WS_OK) return rc;
     WS_HIP(ctx, hipEventRecord(job.ev_done, ctx->stream));
-    job.user_out = out; job.w = ow; job.h = oh; job.out_stride = out_stride; job.dtype = out_dtype;
+    job.user_out = out; job.w = ow; job.h = map_rows; job.row0 = map_row0; job.out_stride = out_stride; job.dtype = out_dtype;
     job.pending = true;
     ctx->job_next ^= 1;
     // the previous pair's map goes down while this one is searched
     return flush_job(ctx, prev);
 }
+
+extern "C" {
 
 int ws_wait(ws_context *ctx)
 {

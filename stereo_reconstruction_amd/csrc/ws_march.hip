@@ -37,6 +37,7 @@
 
 #include <string.h>
 
+#include <atomic>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -75,8 +76,10 @@ static int max_chunks(MarchShape s) { return s.x > 8 ? kMaxT / kMinXRuns : kMaxC
 // 8 x 4 kernel covers half the hypotheses per workgroup and costs 0.62 of an 8 x 8 one (measured: 1.19 .. 1.29 times the
 // time per hypothesis over windows 5 .. 17 at D = 512, profiles/r03/nd_grid.txt).
 // the chip the thread-shape rule plans for: the first context's device (ws_create), 256 CUs without one (ws_plan)
-static int g_model_cus = 256;
-void march_set_num_cus(int n) { if (n > 0) g_model_cus = n; }
+// (atomic: every ws_create writes it and every context's planner reads it, from any thread -- ws_batch_search_host runs
+// several contexts at once; all the devices of a node are the same chip, so whichever write wins the value is the same)
+static std::atomic<int> g_model_cus{256};
+void march_set_num_cus(int n) { if (n > 0) g_model_cus.store(n, std::memory_order_relaxed); }
 
 static double march_model_cost(const Canon &c, MarchShape sh)
 {
@@ -93,7 +96,7 @@ static double march_model_cost(const Canon &c, MarchShape sh)
     for (int sc = 1; sc <= out_h; ++sc) {
         const int rows = ceil_div(out_h, sc), st = ceil_div(out_h, rows);
         if (st != sc) continue;
-        const double cost = ceil_div(tiles * st, g_model_cus) * (rows + 0.5 * (c.wh - 1) + 3.0);
+        const double cost = ceil_div(tiles * st, g_model_cus.load(std::memory_order_relaxed)) * (rows + 0.5 * (c.wh - 1) + 3.0);
         if (sc == 1 || cost < best) best = cost;
     }
     return best * passes * (same_shape(sh, kShapeNarrow) ? 0.62 : 1.0);
@@ -137,7 +140,7 @@ static MarchShape march_shape(const Canon &c)
     struct Memo { int key[9]; MarchShape shape; };
     thread_local Memo memo[4] = {};
     thread_local int next = 0;
-    const int key[9] = {c.ox1 - c.ox0, c.oy1 - c.oy0, c.d_hi - c.d_lo + 1, c.ww, c.wh, c.ssd, 1, g_model_cus, 0};
+    const int key[9] = {c.ox1 - c.ox0, c.oy1 - c.oy0, c.d_hi - c.d_lo + 1, c.ww, c.wh, c.ssd, 1, g_model_cus.load(std::memory_order_relaxed), 0};
     for (const Memo &m : memo)
         if (!memcmp(m.key, key, sizeof key)) return m.shape;
     MarchShape sh = march_model_cost(c, kShapeNarrow) < march_model_cost(c, kShapeWide) ? kShapeNarrow : kShapeWide;

@@ -22,6 +22,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ws_stereo.h"
@@ -399,5 +400,104 @@ inline cv::Mat to_cv(const MatF64 &m)
     return out;
 }
 #endif
+
+// Many independent pairs over the devices of a node (ws_batch_*): what main.cpp's loop over a dataset becomes when the
+// pairs are dealt to several GPUs.  One worker -- a context and a host thread -- per entry of `devices` (a device may
+// repeat; empty = every device).  Pairs go whole (longest first, to the least loaded worker) or, where the batch allows
+// it, as row bands (bands = true); every map equals BlockSearch's map of that pair.  Not to be shared between threads.
+//   wsamd::BatchSearch batch({0, 1, 2, 3, 4, 5, 6, 7});
+//   std::vector<wsamd::BatchSearch::Job> jobs;   // {params, left, right} per pair
+//   std::vector<wsamd::MatF64> maps = batch.run(jobs);
+class BatchSearch {
+public:
+    struct Job {
+        ws_params params;
+        Image8UC3 left, right;
+    };
+
+    explicit BatchSearch(const std::vector<int> &devices = {})
+    {
+        ws_batch *b = nullptr;
+        const int rc = ws_batch_create(devices.empty() ? nullptr : devices.data(), static_cast<int>(devices.size()), &b);
+        if (rc != WS_OK) throw Error(rc, ws_batch_last_error(nullptr));
+        batch_.reset(b);
+    }
+    int workers() const { return ws_batch_workers(batch_.get(), nullptr, 0); }
+
+    // ws_params for one pair: BlockSearch's constructor and method arguments (view = WS_VIEW_LEFT / WS_VIEW_RIGHT)
+    static ws_params params(int view, int blockSize, int minDisparity, int maxDisparity, double smoothFactor)
+    {
+        ws_params p;
+        ws_params_default(&p);
+        p.view = view;
+        p.block_size = blockSize;
+        p.min_disparity = minDisparity;
+        p.max_disparity = maxDisparity;
+        p.smooth_factor = smoothFactor;
+        return p;
+    }
+
+    // CV_64F maps, one per job, in the order of `jobs`
+    std::vector<MatF64> run(const std::vector<Job> &jobs, bool bands = true, int minRows = 256)
+    {
+        std::vector<MatF64> maps;
+        std::vector<ws_job> c(jobs.size());
+        maps.reserve(jobs.size());
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            const Job &j = jobs[i];
+            const bool left = j.params.view == WS_VIEW_LEFT;
+            maps.emplace_back(left ? j.left.rows : j.right.rows, left ? j.left.cols : j.right.cols);
+            c[i] = make_job(j.params, j.left, j.right, maps.back().ptr(), maps.back().cols, WS_OUT_F64);
+        }
+        run(c, bands, minRows);
+        return maps;
+    }
+
+    // caller buffers: each ws_job carries its own `out`; every job's status is set.  Throws the first failed job's error.
+    void run(std::vector<ws_job> &jobs, bool bands = true, int minRows = 256)
+    {
+        const int rc = ws_batch_search_host(batch_.get(), jobs.data(), static_cast<int>(jobs.size()), bands ? 1 : 0, minRows);
+        if (rc != WS_OK) throw Error(rc, ws_batch_last_error(batch_.get()));
+    }
+
+    static ws_job make_job(const ws_params &p, const Image8UC3 &left, const Image8UC3 &right, void *out, int outStride,
+                           int outDtype)
+    {
+        ws_job j;
+        j.params = p;
+        j.left = detail::to_c(left);
+        j.right = detail::to_c(right);
+        j.out = out;
+        j.out_stride = outStride;
+        j.out_dtype = outDtype;
+        j.status = WS_JOB_NOT_RUN;
+        return j;
+    }
+
+#ifdef WSAMD_WITH_OPENCV
+    // cv::Mat pairs (CV_8UC3) with one set of parameters: CV_64F maps, written by the library straight into them
+    std::vector<cv::Mat> run(const ws_params &p, const std::vector<std::pair<cv::Mat, cv::Mat>> &pairs, bool bands = true,
+                             int minRows = 256)
+    {
+        std::vector<cv::Mat> maps;
+        std::vector<ws_job> c;
+        maps.reserve(pairs.size());
+        for (const auto &pr : pairs) {
+            const cv::Mat &size = p.view == WS_VIEW_LEFT ? pr.first : pr.second;
+            maps.emplace_back(size.rows, size.cols, CV_64F);
+            c.push_back(make_job(p, view(pr.first), view(pr.second), maps.back().data,
+                                 static_cast<int>(maps.back().step / sizeof(double)), WS_OUT_F64));
+        }
+        run(c, bands, minRows);
+        return maps;
+    }
+#endif
+
+private:
+    struct Deleter {
+        void operator()(ws_batch *b) const { ws_batch_destroy(b); }
+    };
+    std::unique_ptr<ws_batch, Deleter> batch_;
+};
 
 } // namespace wsamd
