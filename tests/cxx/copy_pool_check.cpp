@@ -1,22 +1,14 @@
-// CPU-only stress of the copy pool of ws_capi.cpp (the class is pasted below by tools/pool_stress.sh):
-//   g++ -O2 -std=c++17 -pthread -fsanitize=thread pool_stress_gen.cpp && ./a.out
-#include <atomic>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <vector>
-#include <string.h>
-#include <stdlib.h>
+// The copy pool of the staging path (stereo_reconstruction_amd/csrc/ws_copy_pool.h) under stress, host only:
+// plain copies, two submitting threads, the three widening kinds and a forked child.  Built and run by
+// tests/test_copy_pool.py with g++ -fsanitize=thread.
+#include "stereo_reconstruction_amd/csrc/ws_copy_pool.h"
+
 #include <stdio.h>
-#include <stdint.h>
-#include <algorithm>
-#include <pthread.h>
-#include <unistd.h>
 #include <sys/wait.h>
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
-//@POOL@
+#include <unistd.h>
+
+using namespace wsamd;
+
 int main()
 {
     const size_t N = 9 << 20;
@@ -66,6 +58,6 @@ int main()
         busy.join();
         if (!WIFEXITED(status) || WEXITSTATUS(status) != 0) { printf("FORKED CHILD FAILED (status %d)\n", status); return 1; }
     }
-    printf("ok\n");
+    printf("copy pool ok\n");
     return 0;
 }

@@ -5,8 +5,9 @@ and, on the GPU box, time bench.py with each of them.
 """
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from stereo_reconstruction_amd import build as libbuild  # noqa: E402  (the library's own list of sources)
 VDIR = os.path.join(ROOT, "gpurun_variants")
-CSRC = os.path.join(ROOT, "stereo_reconstruction_amd", "csrc")
 
 def build(specs):
     os.makedirs(VDIR, exist_ok=True)
@@ -19,8 +20,7 @@ def build(specs):
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-DWS_X=" + x, "-DWS_ND=" + nd, "-DWS_MAXT=" + maxt] + ["-D" + e for e in extra] + flags + [
                "-Rpass-analysis=kernel-resource-usage", "-o", out,
-               ] + [os.path.join(CSRC, f) for f in ("ws_march.hip", "ws_march_nd4.hip", "ws_prepass.hip", "ws_border.hip", "ws_smooth.hip",
-                                                     "ws_consumers.hip", "ws_capi.cpp")]
+               ] + [os.path.join(libbuild.CSRC, f) for f in libbuild.SOURCES]
         r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:
             print(spec, "BUILD FAILED", r.stderr[-2000:]); continue
