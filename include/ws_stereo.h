@@ -268,9 +268,33 @@ int ws_convert_disparity_to_depth(ws_context *ctx, const float *disp, int width,
  */
 int ws_back_project(ws_context *ctx, const float *depth, int width, int height, int stride,
                     const float intrinsics[9], const ws_image *bgr, float *positions, uint8_t *colors);
-/* WriteMesh (reconstruction.cpp:72-149): COFF text file; host only. */
+/*
+ * WriteMesh (reconstruction.cpp:72-149) with CheckTriangularValidity (:46-69): COFF text file -- "COFF", "<w*h> <faces> 0",
+ * one line per vertex ("0 0 0 r g b a" where x is -inf, else "x y z r g b a", floats as `std::ostream << float`, i.e.
+ * printf "%g"), then "3 a b c" for every triangle (i00, i10, i01), (i10, i11, i01) of every grid cell, row-major, whose
+ * three corners are valid and whose edges are all at most edge_threshold long.  This one runs on the host and is what
+ * the device form below is tested against.
+ */
 int ws_write_mesh_off(const char *path, const float *positions, const uint8_t *colors, int width,
                       int height, float edge_threshold);
+/*
+ * The same file, byte for byte, from vertex buffers in device memory (the layout ws_back_project writes: positions
+ * w*h x 4 floats, 16-byte aligned; colors w*h x 4 bytes, 4-byte aligned).  Kernels test the triangles, format every line
+ * and lay the text out; the host only moves the finished bytes into the file, in bounded chunks through pinned memory
+ * of the context.  Orders after `stream` (NULL = the context's own) and returns once the file is written and closed.
+ * WS_ERR_IO if the path cannot be opened (before any device work) or a write fails; WS_ERR_ARG for null pointers,
+ * sizes < 1 or w*h beyond 32-bit vertex indices (UINT32_MAX).
+ */
+int ws_write_mesh_off_device(ws_context *ctx, const float *positions_dev, const uint8_t *colors_dev, int width,
+                             int height, float edge_threshold, const char *path, void *stream);
+/*
+ * reconstruction(bgrImage, depthValues, intrinsics, thrMesh) (reconstruction.cpp:152-208, main.cpp:64) in one
+ * synchronous call: depth and BGR image go up, the vertices are built on the device (as ws_back_project builds them)
+ * and stay there, the mesh text is built by the kernels of ws_write_mesh_off_device and only the text comes down.  The
+ * file is byte-identical to ws_back_project followed by ws_write_mesh_off.  Errors as ws_write_mesh_off_device.
+ */
+int ws_reconstruction_host(ws_context *ctx, const float *depth, int width, int height, int stride,
+                           const float intrinsics[9], const ws_image *bgr, float edge_threshold, const char *path);
 
 /* ---- measurement ------------------------------------------------------------------ */
 /* hipEvent pair on `stream` (NULL = context stream): begin, enqueue work, end -> elapsed ms. */

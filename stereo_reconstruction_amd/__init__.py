@@ -40,7 +40,7 @@ ERRORS = {-1: "WS_ERR_ARG", -2: "WS_ERR_GEOMETRY", -3: "WS_ERR_UNSUPPORTED", -4:
 EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_last_error",
            "ws_device_count", "ws_validate", "ws_plan", "ws_search_host", "ws_search_device", "ws_enqueue_host", "ws_wait", "ws_warp_nearest_host",
            "ws_warp_nearest_device", "ws_remove_disparity_outliers", "ws_convert_disparity_to_depth",
-           "ws_back_project", "ws_write_mesh_off",
+           "ws_back_project", "ws_write_mesh_off", "ws_write_mesh_off_device", "ws_reconstruction_host",
            "ws_timer_begin", "ws_timer_end", "ws_set_profiling", "ws_last_kernel_ms",
            "ws_last_launch_info", "ws_last_max_block", "ws_set_tuning", "ws_set_host_bands", "ws_last_host_paths", "ws_last_wire_format", "ws_last_outliers_path", "ws_device_status",
            "ws_pfm_read", "ws_pfm_write", "ws_free", "ws_ppm_read", "ws_ppm_write", "ws_calib_read", "ws_evaldisp",
@@ -145,6 +145,8 @@ def load_library(build_if_missing=False):
     lib.ws_convert_disparity_to_depth.argtypes = [vp, vp, ci, ci, ci, cf, cf, vp, ci]
     lib.ws_back_project.argtypes = [vp, vp, ci, ci, ci, P(cf), P(_Image), vp, vp]
     lib.ws_write_mesh_off.argtypes = [ctypes.c_char_p, vp, vp, ci, ci, cf]
+    lib.ws_write_mesh_off_device.argtypes = [vp, vp, vp, ci, ci, cf, ctypes.c_char_p, vp]
+    lib.ws_reconstruction_host.argtypes = [vp, vp, ci, ci, ci, P(cf), P(_Image), cf, ctypes.c_char_p]
     lib.ws_warp_nearest_host.argtypes = [vp, vp, ci, ci, ci, P(ctypes.c_double), vp, ci, ci, ci]
     lib.ws_warp_nearest_device.argtypes = [vp, vp, ci, ci, ci, P(ctypes.c_double), vp, ci, ci, ci, vp]
     lib.ws_timer_begin.argtypes = [vp, vp]
@@ -360,6 +362,32 @@ class WindowSearch:
         self._check(self._lib.ws_back_project(self._h, z.ctypes.data, z.shape[1], z.shape[0], z.shape[1], k,
                                               ctypes.byref(hdr), pos.ctypes.data, col.ctypes.data))
         return pos, col
+
+    def reconstruction(self, depth, intrinsics, bgr, edge_threshold, path):
+        """ws_reconstruction_host: reconstruction(bgrImage, depthValues, intrinsics, thrMesh) (reconstruction.cpp:152-208)
+        -- back-projection and the COFF mesh text on the device, the file written at `path`.  The same bytes as
+        back_project() followed by write_mesh_off()."""
+        z = np.ascontiguousarray(depth, dtype=np.float32)
+        img, hdr = _host_image(bgr)
+        k = (ctypes.c_float * 9)(*np.asarray(intrinsics, dtype=np.float32).reshape(9))
+        self._check(self._lib.ws_reconstruction_host(self._h, z.ctypes.data, z.shape[1], z.shape[0], z.shape[1], k,
+                                                     ctypes.byref(hdr), edge_threshold, os.fsencode(path)))
+
+    def write_mesh_off_device(self, positions_t, colors_t, edge_threshold, path, stream=None):
+        """ws_write_mesh_off_device: write_mesh_off() of vertex buffers on the device -- positions_t a float32 CUDA tensor
+        H x W x 4, colors_t a uint8 CUDA tensor H x W x 4, both contiguous.  Orders after `stream` (a hipStream_t handle;
+        None = the context's own, NON-BLOCKING stream: pass torch.cuda.current_stream().cuda_stream or synchronise
+        first) and returns once the file is written."""
+        for t, dt, what in ((positions_t, "float32", "positions"), (colors_t, "uint8", "colors")):
+            if not t.is_cuda or str(t.dtype) != "torch." + dt:
+                raise ValueError("%s: expected a %s CUDA tensor, got %s on %s" % (what, dt, t.dtype, t.device))
+            if t.dim() != 3 or t.shape[2] != 4 or not t.is_contiguous():
+                raise ValueError("%s: expected a contiguous H x W x 4 tensor" % what)
+        if tuple(positions_t.shape) != tuple(colors_t.shape):
+            raise ValueError("positions and colors differ in shape")
+        h, w = positions_t.shape[:2]
+        self._check(self._lib.ws_write_mesh_off_device(self._h, positions_t.data_ptr(), colors_t.data_ptr(), w, h,
+                                                       edge_threshold, os.fsencode(path), ctypes.c_void_p(stream or 0)))
 
     def timer_begin(self, stream=None):
         self._check(self._lib.ws_timer_begin(self._h, ctypes.c_void_p(stream or 0)))

@@ -9,6 +9,7 @@
 #include "ws_capi_internal.h"
 #include "ws_staging.h"
 
+#include <errno.h>
 #include <float.h>
 #include <math.h>
 #include <stdarg.h>
@@ -83,6 +84,9 @@ struct ws_context {
     bool profiling = false, kernel_timed = false;
     DevBuf plane_a, plane_b, keys, cost, bs_plane, max_block, sel, sel_planes, top3, d_left, d_right, d_out, d_out64 /* the consumers' scratch */, d_out16;
     DevBuf d_rect_left, d_rect_right; // ws_search_unrectified_host: the rectified images
+    DevBuf d_mesh, d_mesh_text;       // the mesh text (ws_mesh.hip): per-workgroup sums / offsets and the file's bytes
+    HostBuf h_mesh[2];                // ... which come down through these two pinned chunks (kMeshChunk each)
+    hipEvent_t ev_mesh[2] = {};       // a chunk has landed in h_mesh[i]
     Job jobs[2];             // ws_enqueue_host alternates between two slots
     int job_next = 0;
     hipStream_t copy_stream = nullptr; // host <-> device copies of the batched path, beside the searches
@@ -594,6 +598,8 @@ void ws_destroy(ws_context *ctx)
     for (int i = 0; i < ws_context::kMaxBands; ++i)
         for (hipEvent_t e : {ctx->ev_band_up[i], ctx->ev_band_done[i], ctx->ev_band_down[i]})
             if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ev_mesh)
+        if (e) (void)hipEventDestroy(e);
     // every buffer goes with its owner, on this device, with nothing using it.  A batch never waited for: its maps are NOT
     // handed over -- only ws_wait delivers, and a caller who abandoned the batch may have freed the buffers they go to
     delete ctx;
@@ -1214,6 +1220,155 @@ int ws_back_project(ws_context *ctx, const float *depth, int width, int height, 
 {
     if (!positions || !colors) return ctx ? fail(ctx, WS_ERR_ARG, "null vertex output") : WS_ERR_ARG;
     return depth_vertices_host(ctx, depth, width, height, stride, 1, 0.0f, 0.0f, intrinsics, bgr, nullptr, 0, positions, colors);
+}
+
+// ---- WriteMesh (reconstruction.cpp:72-149) on the device: the kernels of ws_mesh.hip lay out the file's text, the host
+// only moves the finished bytes into the file ------------------------------------------------------------------------
+
+static constexpr size_t kMeshChunk = 8u << 20; // the text comes down in chunks of this size: pinned memory stays 2 chunks
+
+static int mesh_args(ws_context *ctx, const void *pos, const void *col, int width, int height, const char *path)
+{
+    if (!path) return fail(ctx, WS_ERR_ARG, "null mesh path");
+    if (!pos || !col) return fail(ctx, WS_ERR_ARG, "null input buffer");
+    if (width <= 0 || height <= 0) return fail(ctx, WS_ERR_ARG, "bad mesh size %d x %d", width, height);
+    if ((uint64_t)width * (uint64_t)height > UINT32_MAX)
+        return fail(ctx, WS_ERR_ARG, "a %d x %d mesh has more vertices than 32-bit indices reach", width, height);
+    return WS_OK;
+}
+
+static FILE *mesh_open(ws_context *ctx, const char *path, int *rc)
+{
+    FILE *f = fopen(path, "wb");
+    *rc = f ? WS_OK : fail(ctx, WS_ERR_IO, "cannot open %s: %s", path, strerror(errno));
+    return f;
+}
+
+// The end of a mesh call: the stream idle (a failed call may have copies in flight into the chunks), the file closed.
+static int mesh_close(ws_context *ctx, int rc, FILE *f, hipStream_t s)
+{
+    if (rc != WS_OK) (void)hipStreamSynchronize(s);
+    if (fclose(f) != 0 && rc == WS_OK) rc = fail(ctx, WS_ERR_IO, "closing the mesh file failed: %s", strerror(errno));
+    return rc;
+}
+
+// The COFF text of the w x h vertices at dpos / dcol (device) -> the open file f; everything on stream s.  The kernels
+// measure and lay out the text, one synchronisation fetches its size, the text comes down chunk by chunk through two
+// pinned stages and each chunk is written while the next one is in flight.
+static int mesh_to_file(ws_context *ctx, const float *dpos, const uint8_t *dcol, int w, int h, float thr, FILE *f, hipStream_t s)
+{
+    HostTrace tr; // WS_HOST_TRACE=1: when the text's size was known, time waited for chunks (the write kernel included), time writing
+    const size_t nb = mesh_blocks(w, h);
+    int rc;
+    if ((rc = ensure(ctx, ctx->d_mesh, 64 + nb * 16)) != WS_OK) return rc;
+    for (HostBuf &b : ctx->h_mesh) WS_HIP(ctx, host_ensure(b, kMeshChunk));
+    for (hipEvent_t &e : ctx->ev_mesh)
+        if (!e) WS_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    uint8_t *base = static_cast<uint8_t *>(ctx->d_mesh.p);
+    auto *meta = reinterpret_cast<unsigned long long *>(base);             // {header bytes, file bytes, faces}
+    auto *sums = reinterpret_cast<uint32_t *>(base + 64);                  // 2 words per workgroup
+    auto *offs = reinterpret_cast<unsigned long long *>(base + 64 + nb * 8); // 1 word per workgroup
+    WS_HIP(ctx, launch_mesh_count(dpos, dcol, w, h, thr, sums, offs, meta, s));
+    WS_HIP(ctx, hipMemcpyAsync(ctx->h_mesh[0].p, meta, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    WS_HIP(ctx, hipStreamSynchronize(s));
+    unsigned long long hm[3];
+    memcpy(hm, ctx->h_mesh[0].p, sizeof hm);
+    tr.mark("sized");
+    const size_t bytes = (size_t)hm[1];
+    if ((rc = ensure(ctx, ctx->d_mesh_text, bytes)) != WS_OK) return rc;
+    const char *text = static_cast<const char *>(ctx->d_mesh_text.p);
+    WS_HIP(ctx, launch_mesh_write(dpos, dcol, w, h, thr, offs, meta, static_cast<char *>(ctx->d_mesh_text.p), s));
+    double us_wait = 0, us_write = 0;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    int pending = -1; // the chunk that has been enqueued but not yet written to the file
+    size_t pending_len = 0;
+    for (size_t off = 0, k = 0; off < bytes || pending >= 0; ++k) {
+        int cur = -1;
+        size_t len = 0;
+        if (off < bytes) {
+            cur = (int)(k & 1);
+            len = std::min(kMeshChunk, bytes - off);
+            WS_HIP(ctx, hipMemcpyAsync(ctx->h_mesh[cur].p, text + off, len, hipMemcpyDeviceToHost, s));
+            WS_HIP(ctx, hipEventRecord(ctx->ev_mesh[cur], s));
+            off += len;
+        }
+        if (pending >= 0) {
+            const auto t0 = now();
+            WS_HIP(ctx, hipEventSynchronize(ctx->ev_mesh[pending]));
+            const auto t1 = now();
+            if (fwrite(ctx->h_mesh[pending].p, 1, pending_len, f) != pending_len)
+                return fail(ctx, WS_ERR_IO, "writing the mesh file failed: %s", strerror(errno));
+            us_wait += std::chrono::duration<double, std::micro>(t1 - t0).count();
+            us_write += std::chrono::duration<double, std::micro>(now() - t1).count();
+        }
+        pending = cur;
+        pending_len = len;
+    }
+    if (tr.on) {
+        char buf[96];
+        snprintf(buf, sizeof buf, " chunk_wait_total=%.0f fwrite_total=%.0f bytes=%zu", us_wait, us_write, bytes);
+        tr.line += buf;
+    }
+    return WS_OK;
+}
+
+int ws_write_mesh_off_device(ws_context *ctx, const float *positions_dev, const uint8_t *colors_dev, int width, int height,
+                             float edge_threshold, const char *path, void *stream)
+{
+    if (!ctx) return WS_ERR_ARG;
+    int rc = mesh_args(ctx, positions_dev, colors_dev, width, height, path);
+    if (rc != WS_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(positions_dev) & 15) || (reinterpret_cast<uintptr_t>(colors_dev) & 3))
+        return fail(ctx, WS_ERR_ARG, "positions must be 16-byte aligned, colors 4-byte aligned");
+    FILE *f = mesh_open(ctx, path, &rc);
+    if (!f) return rc;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = [&]() -> int {
+        WS_HIP(ctx, hipSetDevice(ctx->device));
+        return mesh_to_file(ctx, positions_dev, colors_dev, width, height, edge_threshold, f, s);
+    }();
+    return mesh_close(ctx, rc, f, s);
+}
+
+int ws_reconstruction_host(ws_context *ctx, const float *depth, int width, int height, int stride, const float intrinsics[9],
+                           const ws_image *bgr, float edge_threshold, const char *path)
+{
+    if (!ctx) return WS_ERR_ARG;
+    int rc = mesh_args(ctx, depth, bgr, width, height, path);
+    if (rc != WS_OK) return rc;
+    if (stride < width) return fail(ctx, WS_ERR_ARG, "bad depth stride");
+    if (!intrinsics || !bgr->data || bgr->width != width || bgr->height != height || bgr->stride < 3 * width)
+        return fail(ctx, WS_ERR_ARG, "reconstruction needs K and a colour image of the depth map's size");
+    FILE *f = mesh_open(ctx, path, &rc);
+    if (!f) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t n = (size_t)width * height;
+    // as ws_back_project, without the vertices' way down: depth and image go up (HostSpan), the vertices stay on the device
+    HostSpan sp[2];
+    rc = [&]() -> int {
+        WS_HIP(ctx, hipSetDevice(ctx->device));
+        int r;
+        if ((r = ensure(ctx, ctx->d_out, n * 4)) != WS_OK) return r;
+        if ((r = ensure(ctx, ctx->d_out64, n * 20)) != WS_OK) return r;
+        return ensure(ctx, ctx->d_left, image_span(sp[1], bgr, &ctx->h_left));
+    }();
+    if (rc != WS_OK) return mesh_close(ctx, rc, f, s);
+    float *din = static_cast<float *>(ctx->d_out.p);
+    uint8_t *vbase = static_cast<uint8_t *>(ctx->d_out64.p);
+    float *dpos = reinterpret_cast<float *>(vbase); // n * 16 bytes, 16-byte aligned
+    uint8_t *dcol = vbase + n * 16;                 // n * 4
+    sp[0].p = reinterpret_cast<uint8_t *>(const_cast<float *>(depth)); sp[0].n = ((size_t)stride * (height - 1) + width) * 4; sp[0].stage = &ctx->h_out;
+    spans_attach(sp, 2);
+    rc = [&]() -> int {
+        WS_HIP(ctx, span_upload_rows(sp[0], 0, (size_t)stride * 4, din, (size_t)width * 4, (size_t)height, s));
+        ws_image dbgr{static_cast<const uint8_t *>(ctx->d_left.p), width, height, width * 3};
+        WS_HIP(ctx, upload_image(sp[1], bgr, static_cast<uint8_t *>(ctx->d_left.p), s, &dbgr));
+        WS_HIP(ctx, launch_depth_vertices(din, width, width, height, 0.0f, 0.0f, intrinsics, dbgr.data, dbgr.stride, nullptr, width,
+                                          dpos, dcol, 1, s));
+        return mesh_to_file(ctx, dpos, dcol, width, height, edge_threshold, f, s);
+    }();
+    rc = finish_host_call(ctx, rc, sp, 2, {s}, "reconstruction");
+    return mesh_close(ctx, rc, f, s);
 }
 
 int ws_timer_begin(ws_context *ctx, void *stream)

@@ -1,5 +1,5 @@
 // ws_kernels.h -- launch interface between the C-ABI host code (ws_capi.cpp) and the
-// gfx950 kernels (ws_march / ws_prepass / ws_border / ws_smooth / ws_consumers .hip).  Internal; the public boundary is include/ws_stereo.h.
+// gfx950 kernels (ws_march / ws_prepass / ws_border / ws_smooth / ws_consumers / ws_mesh .hip).  Internal; the public boundary is include/ws_stereo.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -136,6 +136,15 @@ hipError_t launch_outliers_u32(float *map, int mp, int w, int h, int k, float th
 hipError_t launch_depth_vertices(const float *disp, int dp, int w, int h, float focal, float baseline, const float k[9],
                                  const uint8_t *bgr, int bstride, float *depth, int zp, float *pos, uint8_t *col,
                                  int input_is_depth, hipStream_t s);
+// WriteMesh (reconstruction.cpp:72-149) on the device (ws_mesh.hip): the COFF text of a w x h vertex grid (pos: w*h
+// float4, 16-byte aligned; col: w*h uchar4, 4-byte aligned; w*h <= UINT32_MAX).  launch_mesh_count: sums = 2 words per
+// workgroup of mesh_blocks(w, h), block_off = 1 word per workgroup, meta = {header bytes, file bytes, faces} on the
+// device.  launch_mesh_write then writes meta[1] bytes of text (the whole file) from the same inputs.
+size_t mesh_blocks(int w, int h);
+hipError_t launch_mesh_count(const float *pos, const uint8_t *col, int w, int h, float thr, uint32_t *sums,
+                             unsigned long long *block_off, unsigned long long *meta, hipStream_t s);
+hipError_t launch_mesh_write(const float *pos, const uint8_t *col, int w, int h, float thr, const unsigned long long *block_off,
+                             const unsigned long long *meta, char *text, hipStream_t s);
 // varBlock (BlockSearch.cpp:125-145, right view): per-pixel window growth + search, one wave per pixel.
 // bs_plane: w2 x h2 int16 (pitch bs_pitch), max_block: one device int (max grown block size)
 hipError_t launch_varblock(const GenericArgs &g, double thres, int16_t *bs_plane, int bs_pitch, int *max_block,

@@ -371,19 +371,16 @@ inline MatF32 convertDisparityToDepth(const MatF32 &dispImage, float focalLength
 }
 
 // reconstruction(bgrImage, depthValues, intrinsics, thrMesh) (reconstruction.cpp:152-208); the
-// reference's hard-coded output path becomes an argument.
+// reference's hard-coded output path becomes an argument.  One call (ws_reconstruction_host): the vertices and the
+// mesh text are built on the device, only the text comes back to be written.
 inline void reconstruction(const Image8UC3 &bgrImage, const MatF32 &depthValues, const float intrinsics[9],
                            float thrMesh, const std::string &meshPath, Device &device = Device::shared())
 {
-    const size_t n = static_cast<size_t>(depthValues.rows) * depthValues.cols;
-    std::vector<float> positions(4 * n);
-    std::vector<uint8_t> colors(4 * n);
     const ws_image img = detail::to_c(bgrImage);
-    int rc = ws_back_project(device.get(), depthValues.ptr(), depthValues.cols, depthValues.rows, depthValues.cols,
-                             intrinsics, &img, positions.data(), colors.data());
+    const int rc = ws_reconstruction_host(device.get(), depthValues.ptr(), depthValues.cols, depthValues.rows,
+                                          depthValues.cols, intrinsics, &img, thrMesh, meshPath.c_str());
+    if (rc == WS_ERR_IO) throw Error(rc, "Failed to write mesh! Check file path!");
     if (rc != WS_OK) throw Error(rc, ws_last_error(device.get()));
-    rc = ws_write_mesh_off(meshPath.c_str(), positions.data(), colors.data(), depthValues.cols, depthValues.rows, thrMesh);
-    if (rc != WS_OK) throw Error(rc, "Failed to write mesh! Check file path!");
 }
 
 #ifdef WSAMD_WITH_OPENCV
