@@ -175,8 +175,7 @@ size_t image_span(HostSpan &sp, const ws_image *im, HostBuf *stage)
     sp.stage = stage;
     const size_t rb = (size_t)im->width * 3;
     if (!linear_span(im)) return rb * im->height;
-    sp.p = const_cast<uint8_t *>(im->data);
-    sp.n = (size_t)im->stride * (im->height - 1) + rb;
+    span_set(sp, im->data, im->stride, rb, im->height, stage);
     return sp.n;
 }
 

@@ -65,6 +65,14 @@ struct HostSpan {
     std::vector<Seg> down;    // handed to the caller by spans_finish / span_scatter_seg
 };
 
+// A caller buffer of `rows` rows of `row_bytes`, `pitch` bytes apart, crossing through `stage` when it must.
+inline void span_set(HostSpan &sp, const void *p, size_t pitch, size_t row_bytes, size_t rows, HostBuf *stage)
+{
+    sp.p = static_cast<uint8_t *>(const_cast<void *>(p));
+    sp.n = pitch * (rows - 1) + row_bytes;
+    sp.stage = stage;
+}
+
 // Classify the buffers of one call.  Spans with p == nullptr or n == 0 stay kUnused.
 void spans_attach(HostSpan *sp, int count);
 

@@ -320,6 +320,30 @@ def test_errors(wslib, gpu_ctx):
     assert np.array_equal(got, gpu_ctx.search(p, left, right))
 
 
+def test_unrectified_checks_the_output_before_the_homographies(wslib, gpu_ctx):
+    """The map buffer (pointer, type, stride) is checked with the arguments, before the homographies are inverted and the
+    rectified sizes searched: a call with a bad map buffer AND a singular homography reports the map buffer."""
+    lib = wslib.load_library()
+    left, right, _ = make_pair(64, 40, 8, seed=1)
+    p = wslib.make_params(wslib.VIEW_RIGHT, 5, 0, 8)
+    La, Li = wslib._host_image(left)
+    Ra, Ri = wslib._host_image(right)
+    eye = (ctypes.c_double * 9)(*np.eye(3).reshape(9))
+    singular = (ctypes.c_double * 9)(*np.array([[1.0, 2.0, 0.0], [2.0, 4.0, 0.0], [0.0, 0.0, 1.0]]).reshape(9))
+    out = np.empty(right.shape[:2], dtype=np.float64)
+    h = gpu_ctx._h
+
+    def message(H, out_ptr, stride):
+        rc = lib.ws_search_unrectified_host(h, ctypes.byref(p), ctypes.byref(Li), ctypes.byref(Ri), H, eye, out_ptr, stride,
+                                            1, None, 0, None, 0)
+        assert rc == -1
+        return lib.ws_last_error(h).decode()
+
+    assert "singular homography" in message(singular, out.ctypes.data, 64)
+    assert message(singular, out.ctypes.data, 63) == "out_stride 63 < width 64"
+    assert message(singular, None, 63) == "bad output"
+
+
 # ---- the C++ facade -------------------------------------------------------------------------------------------------
 
 def test_cxx_image_rectifier_equals_the_python_call(wslib, gpu_ctx, tmp_path):

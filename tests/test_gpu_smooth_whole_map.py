@@ -111,8 +111,8 @@ def _check(wslib, ctx, view, key, bs, mind, maxd, s, cost="ssd", rows=(), cols=(
 
 
 # The right view's smoothFactor path runs its data-parallel search (the marching kernel, whose planes and cost plane
-# the prepare kernels read) with min_disparity 1: d = 0 is decided by the prepare / resolve passes (run_device_on,
-# ws_capi.cpp).  The plan of that launch is the plan with mind = SMOOTH_RIGHT_MIND.
+# the prepare kernels read) with min_disparity 1: d = 0 is decided by the prepare / resolve passes (search_on,
+# ws_search.cpp).  The plan of that launch is the plan with mind = SMOOTH_RIGHT_MIND.
 SMOOTH_RIGHT_MIND = 1
 
 
