@@ -11,6 +11,7 @@ The functions mirror the reference's call surface:
   evaldisp     ~ evaldisp(disp, gt, mask, badthresh, maxdisp, rounddisp)     (utils.cpp:123-168)
   fast_left / fast_right: block_left / block_right bit for bit, in O(H * W * D) whatever the window
     size (oracle/ws_fast.c): whole full-size maps in seconds; no var_block
+  subpixel: False, True (the parabolic refinement in double) or "float32" (rounded as the device rounds it)
 Images are H x W x 3 uint8 arrays (BGR), outputs float64 maps.
 """
 import ctypes
@@ -24,6 +25,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libws_oracle.so")
 
 COST = {"ssd": 0, "sad": 1}
+
+
+def _subpixel(mode):
+    """subpixel=False / True (the refinement in double) / "float32" (as the device's float32 map holds it: the
+    quotient rounded to float and added to d in float, WSO_SUBPIXEL_F32 in ws_oracle.h)."""
+    if isinstance(mode, str):
+        if mode != "float32":
+            raise ValueError("subpixel must be False, True or 'float32', not %r" % (mode,))
+        return 2
+    return 1 if mode else 0
 
 
 class OracleGeometryError(ValueError):
@@ -153,7 +164,7 @@ def block_left(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
     set_threads(threads)
     _check(lib().wso_block_left(ctypes.byref(Li), ctypes.byref(Ri), block_size,
                                 min_disparity, max_disparity, smooth, COST[cost],
-                                int(subpixel), y0, y1, out.ctypes.data, out.shape[1]))
+                                _subpixel(subpixel), y0, y1, out.ctypes.data, out.shape[1]))
     return out
 
 
@@ -168,7 +179,7 @@ def block_right(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
     set_threads(threads)
     _check(lib().wso_block_right(ctypes.byref(Li), ctypes.byref(Ri), block_size,
                                  min_disparity, max_disparity, smooth, int(var_block),
-                                 thres, COST[cost], int(subpixel), y0, y1,
+                                 thres, COST[cost], _subpixel(subpixel), y0, y1,
                                  out.ctypes.data, out.shape[1], ctypes.byref(mb)))
     return (out, mb.value) if return_max_block else out
 
@@ -182,7 +193,7 @@ def fast_left(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
     y0, y1 = _rows(rows, La.shape[0])
     _check(lib().wsf_block_left(ctypes.byref(Li), ctypes.byref(Ri), block_size,
                                 min_disparity, max_disparity, smooth, COST[cost],
-                                int(subpixel), y0, y1, out.ctypes.data, out.shape[1], int(threads or host_threads())))
+                                _subpixel(subpixel), y0, y1, out.ctypes.data, out.shape[1], int(threads or host_threads())))
     return out
 
 
@@ -195,7 +206,7 @@ def fast_right(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
     y0, y1 = _rows(rows, Ra.shape[0])
     _check(lib().wsf_block_right(ctypes.byref(Li), ctypes.byref(Ri), block_size,
                                  min_disparity, max_disparity, smooth, int(var_block),
-                                 COST[cost], int(subpixel), y0, y1,
+                                 COST[cost], _subpixel(subpixel), y0, y1,
                                  out.ctypes.data, out.shape[1], int(threads or host_threads())))
     return out
 

@@ -239,12 +239,17 @@ static int argmin_d(const geom *g, const uint32_t *win, int lo, int hi)
     return hi;
 }
 
-/* the build's parabolic refinement, on the integer costs at d - 1, d, d + 1 */
-static double parabola(uint32_t cm, uint32_t c0, uint32_t cp)
+/* the build's parabolic refinement of d, on the integer costs at d - 1, d, d + 1: the double sum, or for
+ * WSO_SUBPIXEL_F32 the float32 value the device stores (the quotient rounded to float, one float addition) */
+static double parabola(int d, uint32_t cm, uint32_t c0, uint32_t cp, int subpixel)
 {
     double num = (double)cm - (double)cp;
     double den = (double)cm - 2.0 * (double)c0 + (double)cp;
-    return den > 0.0 ? num / (2.0 * den) : 0.0;
+    if (!(den > 0.0)) return (double)d;
+    double q = num / (2.0 * den);
+    if (subpixel != WSO_SUBPIXEL_F32) return (double)d + q;
+    float f = (float)d + (float)q;
+    return (double)f;
 }
 
 /* the reference's dist before smoothing: norm, and for the right view / (ww * wh) (:64-66, :156-158) */
@@ -323,9 +328,7 @@ static void row_plain(const geom *g, work *w, int y, int subpixel, double *orow)
         }
         slide_cols(g, w->col, w->win, &ca, &cb, a, b);
         int d = argmin_d(g, w->win, lo, hi);
-        double v = (double)d;
-        if (subpixel && d > lo && d < hi) v += parabola(wd[d - 1], wd[d], wd[d + 1]);
-        orow[x] = v;
+        orow[x] = subpixel && d > lo && d < hi ? parabola(d, wd[d - 1], wd[d], wd[d + 1], subpixel) : (double)d;
     }
 }
 

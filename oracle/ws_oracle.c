@@ -70,13 +70,24 @@ static inline double norm_of(uint64_t sum, int cost)
     return (cost == WSO_COST_SAD) ? (double)sum : sqrt((double)sum);
 }
 
-/* Build extension: parabola through the aggregated integer cost at d-1,d,d+1. */
+/* Build extension: parabola through the aggregated integer cost at d-1,d,d+1 (the subpixel modes: ws_oracle.h). */
 static double parabola_offset(uint64_t cm, uint64_t c0, uint64_t cp)
 {
     double num = (double)cm - (double)cp;
     double den = (double)cm - 2.0 * (double)c0 + (double)cp;
     if (!(den > 0.0)) return 0.0;
     return num / (2.0 * den);
+}
+
+/* The refined value of integer disparity d: in double, or as the device's float32 map holds it. */
+static double refined_value(int d, uint64_t cm, uint64_t c0, uint64_t cp, int subpixel)
+{
+    double q = parabola_offset(cm, c0, cp);
+    if (subpixel == WSO_SUBPIXEL_F32) {
+        float v = (float)d + (float)q;   /* (q == 0 when den <= 0: v is d) */
+        return (double)v;
+    }
+    return (double)d + q;
 }
 
 int wso_block_left(const wso_image *L, const wso_image *R, int block_size,
@@ -136,7 +147,7 @@ int wso_block_left(const wso_image *L, const wso_image *R, int block_size,
                     uint64_t c0 = window_sum(L, x - half, y - half, R, best_cx - half, y - half, block_size, block_size, cost);
                     uint64_t c_m = window_sum(L, x - half, y - half, R, cm - half, y - half, block_size, block_size, cost);
                     uint64_t c_p = window_sum(L, x - half, y - half, R, cp - half, y - half, block_size, block_size, cost);
-                    value += parabola_offset(c_m, c0, c_p);
+                    value = refined_value(x - best_cx, c_m, c0, c_p, subpixel);
                 }
             }
             out[(size_t)y * out_stride + x] = value;
@@ -261,7 +272,7 @@ int wso_block_right(const wso_image *L, const wso_image *R, int block_size,
                     uint64_t c0 = window_sum(L, best_cx - left, y - up, R, x - left, y - up, ww, wh, cost);
                     uint64_t c_m = window_sum(L, cm - left, y - up, R, x - left, y - up, ww, wh, cost);
                     uint64_t c_p = window_sum(L, cp - left, y - up, R, x - left, y - up, ww, wh, cost);
-                    value += parabola_offset(c_m, c0, c_p);
+                    value = refined_value(best_cx - x, c_m, c0, c_p, subpixel);
                 }
             }
             out[(size_t)y * out_stride + x] = value;

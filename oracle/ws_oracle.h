@@ -43,6 +43,17 @@ enum {
     WSO_ERR_RANGE = -3     /* row band requested together with smoothFactor != 1 */
 };
 
+/*
+ * Values of `subpixel` (the build's parabolic refinement, an extension).  A refined pixel's
+ * value is d + num / (2 den), num = c(d-1) - c(d+1), den = c(d-1) - 2 c(d) + c(d+1), from the
+ * exact integer window costs; den <= 0 leaves d.
+ *   WSO_SUBPIXEL_DOUBLE  the sum in double
+ *   WSO_SUBPIXEL_F32     as the device's float32 map holds it: (float)d + (float)(num / (2.0 * den)),
+ *                        the quotient correctly rounded in double, then to float, then one float
+ *                        addition -- not the double sum rounded to float once (a double rounding)
+ */
+enum { WSO_SUBPIXEL_OFF = 0, WSO_SUBPIXEL_DOUBLE = 1, WSO_SUBPIXEL_F32 = 2 };
+
 typedef struct {
     const uint8_t *data;
     int width;
@@ -64,7 +75,8 @@ void wso_set_threads(int n);
  * legal for smooth == 1.0 (raster dependency otherwise, BlockSearch.cpp:68-73).
  * cost = WSO_COST_SAD is the build's NORM_L1 extension.
  * subpixel != 0 adds the build's parabolic refinement on the aggregated
- * integer cost (extension; smooth must be 1.0).
+ * integer cost (extension; smooth must be 1.0): WSO_SUBPIXEL_F32 rounds it as
+ * the device does, any other non-zero value gives the double result.
  */
 int wso_block_left(const wso_image *L, const wso_image *R, int block_size,
                    int min_disparity, int max_disparity, double smooth,

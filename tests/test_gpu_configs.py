@@ -110,7 +110,8 @@ def test_config4_training_h_shapes(wslib, gpu_ctx, oracle, dmode):
 def test_config5_subpixel_at_full_size(wslib, gpu_ctx, oracle):
     """BASELINE.json configs[4]: 3840 x 2160, 9x9 SSD, D = 1024, parabolic refine.  D = 1024 runs as four
     d-group passes whose keys meet in a plane (ws_march.hip) BEFORE the refine reads the winner: the
-    integer part must be the bit-exact argmin (BlockSearch.cpp:76-82), the fraction within 1e-4."""
+    integer part must be the bit-exact argmin (BlockSearch.cpp:76-82), the fraction within 1e-4 of the double
+    refinement and the float32 value exactly the one the device's arithmetic defines."""
     w, h, bs, maxd = 3840, 2160, 9, 1024
     half = 4
     left, right, gt = make_pair(w, h, maxd, 5)
@@ -131,6 +132,8 @@ def test_config5_subpixel_at_full_size(wslib, gpu_ctx, oracle):
         assert np.array_equal(whole[y0:y1], want_int[y0:y1]), y0
         err = np.abs(sub[y0:y1] - want_sub[y0:y1]).max()
         assert err <= SUBPIXEL_TOL, (y0, err)
+        want_f32 = oracle.block_left(left, right, bs, 0, maxd, cost="ssd", subpixel="float32", rows=(y0, y1), threads=8)
+        assert np.array_equal(sub[y0:y1], want_f32[y0:y1]), (y0, np.argwhere(sub[y0:y1] != want_f32[y0:y1])[:5].tolist())
         # integer part of the refined map == the argmin, recovered without the oracle's own fraction
         assert np.array_equal(np.round(sub[y0:y1] - (want_sub[y0:y1] - want_int[y0:y1])), want_int[y0:y1]), y0
 

@@ -261,6 +261,7 @@ def test_integer_maps_cross_as_16_bit_and_are_widened_on_the_host(wslib, gpu_ctx
     host_call(wslib, gpu_ctx, pq, left, right, out)
     assert gpu_ctx.last_wire_format() == "float32"
     assert np.abs(out - oracle.block_left(left, right, BS, 0, MAXD, subpixel=True)).max() <= 1e-4
+    assert np.array_equal(out, oracle.block_left(left, right, BS, 0, MAXD, subpixel="float32"))
     # in bands (a megapixel and more): band by band through the stage, widened while the next band is searched
     big_l, big_r, _ = make_pair(1100, 1000, 32, seed=341)
     pb = wslib.make_params(wslib.VIEW_LEFT, BS, 0, 32)

@@ -293,6 +293,9 @@ def test_subpixel_within_tolerance(wslib, gpu_ctx, oracle, view, cost):
     got = run(wslib, gpu_ctx, view, left, right, 9, 0, 64, cost, subpixel=True)
     want = ref(oracle, view, left, right, 9, 0, 64, cost, subpixel=True)
     assert np.abs(got - want).max() <= SUBPIXEL_TOL
+    # and bit for bit the float32 value the device's arithmetic defines (d + the fraction rounded to float)
+    want_f32 = ref(oracle, view, left, right, 9, 0, 64, cost, subpixel="float32")
+    assert np.array_equal(got, want_f32), np.argwhere(got != want_f32)[:5].tolist()
     # the integer part is still the bit-exact argmin: the refine adds a fraction in [-0.5, 0.5] to it
     want_int = ref(oracle, view, left, right, 9, 0, 64, cost)
     got_int = run(wslib, gpu_ctx, view, left, right, 9, 0, 64, cost)

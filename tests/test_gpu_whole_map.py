@@ -14,7 +14,8 @@ seam or strip boundary between the sampled rows would pass them.  Here:
   * key-range extremes: windows whose every candidate costs the analytic maximum (only the tie tag decides), one
     candidate one unit below it, D at the last value the marching kernel accepts and the first it refuses, a
     multi-pass D, the smooth path's top-3 table and the brute-force kernel at the largest window (63).
-Integer maps are compared with np.array_equal, sub-pixel maps within 1e-4.
+Integer maps are compared with np.array_equal; sub-pixel maps within 1e-4 of the double refinement and with
+np.array_equal against the float32 value the device's arithmetic defines (tests/test_gpu_subpixel.py).
 """
 import numpy as np
 import pytest
@@ -82,7 +83,7 @@ def test_config3_whole_map_through_the_halo_packed_sad_kernel(wslib, gpu_ctx, or
 
 def test_config5_subpixel_whole_map(wslib, gpu_ctx, oracle):
     """3840 x 2160, 9x9 SSD, D = 1024 in the plan's d-group passes: the integer map is the exact argmin at every pixel,
-    the refined one within 1e-4 of the reference's parabola."""
+    the refined one within 1e-4 of the reference's parabola and equal to its float32 rounding."""
     w, h, bs, cost, maxd, seed = WORKLOADS["config5"]
     left, right, _ = make_pair(w, h, maxd, seed)
     p = wslib.make_params(wslib.VIEW_LEFT, bs, 0, maxd, 1.0, cost)
@@ -95,6 +96,7 @@ def test_config5_subpixel_whole_map(wslib, gpu_ctx, oracle):
     _assert_same(whole, want_int, "config5 integer")
     err = np.abs(sub - want_sub).max()
     assert err <= SUBPIXEL_TOL, err
+    _assert_same(sub, oracle.fast_left(left, right, bs, 0, maxd, cost=cost, subpixel="float32"), "config5 float32")
     # the refined map's integer part is the argmin, recovered with the reference's fraction
     assert np.array_equal(np.round(sub - (want_sub - want_int)), want_int)
 
