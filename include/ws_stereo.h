@@ -198,6 +198,55 @@ int ws_search_unrectified_host(ws_context *ctx, const ws_params *p, const ws_ima
                                const double H[9], const double Hp[9], void *out, int out_stride, int out_dtype,
                                uint8_t *rect_left, int rect_left_stride, uint8_t *rect_right, int rect_right_stride);
 
+/* ---- left-right consistency check and occlusion fill (extension) ----------------------------- */
+/*
+ * Flags the pixels whose disparity the other view does not confirm -- OpenCV's disp12MaxDiff cross-check -- on two
+ * float32 maps:
+ *   A_L, w_L x h_L: left-view convention, pixel x matches right column x - d  (BlockSearch.cpp:82);
+ *   A_R, w_R x h_R: right-view convention, pixel x matches left column x + d  (BlockSearch.cpp:174).
+ * For each pixel (y, x) of one map with value v, B is the other map and s = -1 for the left map, +1 for the right map.
+ *   1. Empty: v == 0 (-0.0 included) means no disparity.  The output is 0; the pixel is not counted and is never a fill
+ *      source.
+ *   2. Fail: the pixel fails if v is not finite, or y >= h_B, or the partner column p = x + s * rint(v) lies outside
+ *      [0, w_B).  rint rounds half to even (rintf, np.rint); p is computed without integer overflow.
+ *   3. Otherwise the pixel passes iff fabsf(v - B(y, p)) <= max_diff, in float32: a NaN partner fails, a partner of 0
+ *      fails unless |v| <= max_diff.
+ *   4. A pixel that passes keeps v.  A failed pixel becomes 0 (WS_LR_FILL_NONE), or (WS_LR_FILL_BACKGROUND) takes the
+ *      nearest pixel that passed on the same output row to its left and the nearest to its right: both present, fminf
+ *      of their values (the farther surface); one present, its value; neither, 0.  Only pixels that passed are fill
+ *      sources: filled pixels never feed other pixels.
+ *   5. The count of a map is the number of its pixels that failed (filled pixels included).
+ * max_diff >= 0 (+inf allowed); NaN or negative is WS_ERR_ARG.  An output that overlaps an input or the other output is
+ * WS_ERR_ARG.  The rules need no search: they apply to any two maps (sub-pixel maps, maps read from PFM).  A checked map
+ * feeds ws_convert_disparity_to_depth as it is: 0 becomes -inf and the mesh drops that vertex (reconstruction.cpp:30-43).
+ */
+enum { WS_LR_FILL_NONE = 0, WS_LR_FILL_BACKGROUND = 1 };
+typedef struct {
+    float max_diff; /* the largest |v - partner| that passes (disp12MaxDiff) */
+    int fill;       /* WS_LR_FILL_* */
+} ws_lr_params;
+
+/* The check alone, on maps in device memory (strides in elements).  Only enqueues, on `stream` (NULL = the context's own). */
+int ws_lr_check_device(ws_context *ctx, const float *left_dev, int lw, int lh, int lstride,
+                       const float *right_dev, int rw, int rh, int rstride, const ws_lr_params *lr,
+                       float *out_left_dev, int out_lstride, float *out_right_dev, int out_rstride, void *stream);
+/*
+ * Both block-search views of one pair, then the check, on host buffers; synchronous.  p->view is ignored: the call runs p
+ * as WS_VIEW_LEFT and then as WS_VIEW_RIGHT, every other field as given, each map bit-identical to ws_search_host's for
+ * that view.  Each view's parameters are checked as ws_search_host checks them; the first refusal is returned, left
+ * first.  The images go up once; both checked maps come down as out_dtype (F64: the float32 map widened).
+ * out_left: h_L x w_L, out_right: h_R x w_R elements, strides in elements.
+ */
+int ws_search_lr_host(ws_context *ctx, const ws_params *p, const ws_image *left, const ws_image *right,
+                      const ws_lr_params *lr, void *out_left, int out_lstride, void *out_right, int out_rstride,
+                      int out_dtype);
+/* The same on device images and float32 device maps.  Only enqueues; ws_device_status reports the left view's raster pass. */
+int ws_search_lr_device(ws_context *ctx, const ws_params *p, const ws_image *left_dev, const ws_image *right_dev,
+                        const ws_lr_params *lr, float *out_left_dev, int out_lstride, float *out_right_dev,
+                        int out_rstride, void *stream);
+/* Pixels that failed in the last check of this context, {left, right}; waits for that check's stream. */
+int ws_last_lr_counts(ws_context *ctx, unsigned long long counts[2]);
+
 /* ---- many pairs over the devices of a node ------------------------------------------------ */
 /*
  * Independent pairs are dealt to WORKERS: one ws_context and one host thread each.  Workers are device indices; a device

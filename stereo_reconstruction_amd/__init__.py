@@ -46,7 +46,7 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_pfm_read", "ws_pfm_write", "ws_free", "ws_ppm_read", "ws_ppm_write", "ws_calib_read", "ws_evaldisp",
            "ws_rectified_size", "ws_rectify_device", "ws_search_unrectified_host",
            "ws_batch_create", "ws_batch_destroy", "ws_batch_last_error", "ws_batch_workers", "ws_batch_plan",
-           "ws_batch_search_host"]
+           "ws_batch_search_host", "ws_lr_check_device", "ws_search_lr_host", "ws_search_lr_device", "ws_last_lr_counts"]
 JOB_NOT_RUN = 1  # ws_job.status of a job its worker never reached (WS_JOB_NOT_RUN)
 
 
@@ -67,6 +67,19 @@ class _Params(ctypes.Structure):
                 ("smooth_factor", ctypes.c_double), ("var_block", ctypes.c_int),
                 ("thres", ctypes.c_double), ("subpixel", ctypes.c_int),
                 ("linear_range", ctypes.c_int)]
+
+
+class _LrParams(ctypes.Structure):
+    _fields_ = [("max_diff", ctypes.c_float), ("fill", ctypes.c_int)]
+
+
+LR_FILL_NONE, LR_FILL_BACKGROUND = 0, 1
+
+
+def lr_params(max_diff=1.0, fill=False):
+    """ws_lr_params: the largest |v - partner| that passes the left-right check; fill=True fills failed pixels from
+    the nearest passed pixels of their row (WS_LR_FILL_BACKGROUND), else they become 0."""
+    return _LrParams(max_diff, LR_FILL_BACKGROUND if fill else LR_FILL_NONE)
 
 
 class _Job(ctypes.Structure):
@@ -182,6 +195,10 @@ def load_library(build_if_missing=False):
     lib.ws_batch_workers.argtypes = [vp, P(ci), ci]
     lib.ws_batch_plan.argtypes = [P(_Job), ci, ci, ci, ci, P(_BatchItem), ci, P(ci), P(ci)]
     lib.ws_batch_search_host.argtypes = [vp, P(_Job), ci, ci, ci]
+    lib.ws_lr_check_device.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, P(_LrParams), vp, ci, vp, ci, vp]
+    lib.ws_search_lr_host.argtypes = [vp, P(_Params), P(_Image), P(_Image), P(_LrParams), vp, ci, vp, ci, ci]
+    lib.ws_search_lr_device.argtypes = [vp, P(_Params), P(_Image), P(_Image), P(_LrParams), vp, ci, vp, ci, vp]
+    lib.ws_last_lr_counts.argtypes = [vp, P(ctypes.c_ulonglong)]
     _lib = lib
     return lib
 
@@ -292,6 +309,52 @@ class WindowSearch:
                                                ctypes.c_void_p(stream or 0)))
         if check:
             self.device_status(stream)
+
+    # -- left-right consistency check (extension; rules in include/ws_stereo.h) -------------------
+    def search_lr(self, params, left, right, max_diff=1.0, fill=False, dtype=np.float64):
+        """ws_search_lr_host: both block-search views of the pair (params.view is ignored), then the left-right check.
+        Returns (left_map, right_map); failed pixels are 0, or filled from their row's passed pixels with fill=True."""
+        La, Li = _host_image(left)
+        Ra, Ri = _host_image(right)
+        if dtype not in (np.float32, np.float64):
+            raise ValueError("dtype must be float32 or float64")
+        outl = np.empty(La.shape[:2], dtype=dtype)
+        outr = np.empty(Ra.shape[:2], dtype=dtype)
+        lr = lr_params(max_diff, fill)
+        self._check(self._lib.ws_search_lr_host(self._h, ctypes.byref(params), ctypes.byref(Li), ctypes.byref(Ri),
+                                                ctypes.byref(lr), outl.ctypes.data, outl.shape[1], outr.ctypes.data,
+                                                outr.shape[1], OUT_F64 if dtype == np.float64 else OUT_F32))
+        return outl, outr
+
+    def search_lr_device(self, params, left_t, right_t, out_left_t, out_right_t, max_diff=1.0, fill=False, stream=None,
+                         check=False):
+        """ws_search_lr_device on uint8 CUDA images and float32 CUDA maps (as search_device).  Only enqueues."""
+        Li = _Image(left_t.data_ptr(), left_t.shape[1], left_t.shape[0], left_t.stride(0))
+        Ri = _Image(right_t.data_ptr(), right_t.shape[1], right_t.shape[0], right_t.stride(0))
+        lr = lr_params(max_diff, fill)
+        self._check(self._lib.ws_search_lr_device(self._h, ctypes.byref(params), ctypes.byref(Li), ctypes.byref(Ri),
+                                                  ctypes.byref(lr), out_left_t.data_ptr(), out_left_t.stride(0),
+                                                  out_right_t.data_ptr(), out_right_t.stride(0), ctypes.c_void_p(stream or 0)))
+        if check:
+            self.device_status(stream)
+
+    def lr_check_device(self, left_t, right_t, out_left_t, out_right_t, max_diff=1.0, fill=False, stream=None):
+        """ws_lr_check_device on float32 CUDA maps (H x W, rows may be padded).  Only enqueues on `stream`."""
+        for t in (left_t, right_t, out_left_t, out_right_t):
+            if t.dim() != 2 or t.stride(1) != 1 or t.element_size() != 4 or not t.is_floating_point():
+                raise ValueError("expected float32 H x W tensors with dense rows")
+        lr = lr_params(max_diff, fill)
+        self._check(self._lib.ws_lr_check_device(
+            self._h, left_t.data_ptr(), left_t.shape[1], left_t.shape[0], left_t.stride(0),
+            right_t.data_ptr(), right_t.shape[1], right_t.shape[0], right_t.stride(0), ctypes.byref(lr),
+            out_left_t.data_ptr(), out_left_t.stride(0), out_right_t.data_ptr(), out_right_t.stride(0),
+            ctypes.c_void_p(stream or 0)))
+
+    def last_lr_counts(self):
+        """ws_last_lr_counts: (failed pixels of the left map, of the right map) in the last check of this context."""
+        c = (ctypes.c_ulonglong * 2)()
+        self._check(self._lib.ws_last_lr_counts(self._h, c))
+        return int(c[0]), int(c[1])
 
     def warp_nearest(self, src, matrix, dst_shape):
         """cv::warpPerspective(src, dst, matrix, dst_size, INTER_NEAREST) on a float64 map."""
@@ -619,6 +682,13 @@ class BlockSearch:
         p = make_params(VIEW_RIGHT, self.blockSize_, self.minDisparity_, self.maxDisparity_,
                         smoothFactor, self.cost, varBlock, thres, self.subpixel)
         return _ctx(self._context).search(p, self.leftImage_, self.rightImage_)
+
+    def computeDisparityMapsChecked(self, smoothFactor, maxDiff=1.0, fill=False, varBlock=False, thres=19.0):
+        """Extension: both views (computeDisparityMapLeft / Right with these arguments) and the left-right check
+        (disp12MaxDiff = maxDiff).  Returns (left_map, right_map) as float64; failed pixels are 0 or filled."""
+        p = make_params(VIEW_LEFT, self.blockSize_, self.minDisparity_, self.maxDisparity_,
+                        smoothFactor, self.cost, varBlock, thres, self.subpixel)
+        return _ctx(self._context).search_lr(p, self.leftImage_, self.rightImage_, maxDiff, fill)
 
 
 class LinearSearch:

@@ -1,12 +1,14 @@
 // ws_capi.cpp -- the C-ABI of include/ws_stereo.h: the context, the entry points that run the search dispatch
 // (ws_search.h) on device memory or on the caller's host buffers (through ws_staging.h), and the rectify, consumer and
-// mesh calls.  Compiled with hipcc; no compute happens on the host.
+// mesh calls.  Compiled with hipcc; no compute happens on the host.  The context is defined in ws_context.h; the
+// left-right check's entry points are in ws_lr.cpp.
 // The Middlebury plumbing (PFM, calib.txt, evaldisp) is in ws_io.cpp.
 #include "../../include/ws_stereo.h"
 #include "ws_kernels.h"
 #include "ws_rectify.h"
 #include "ws_search.h"
 #include "ws_staging.h"
+#include "ws_context.h"
 
 #include <errno.h>
 #include <float.h>
@@ -25,20 +27,6 @@
 using namespace wsamd;
 
 namespace {
-
-struct Job { // one pair in flight on the batched host path
-    DevBuf in;               // left image, then right image (rows with the caller's stride, or gathered dense)
-    DevBuf out, out16;       // the map as float32 / int16
-    int wire = 0;            // the wire format this pair's map comes down in
-    hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
-    void *user_out = nullptr;
-    int w = 0, h = 0, out_stride = 0, dtype = 0;
-    int row0 = 0;         // the first row of the device map that goes to user_out (a row band: its halo rows stay behind)
-    bool pending = false; // searched (or being searched), result not yet on its way to user_out
-    HostBuf h_left, h_right; // stages of the images, or their gathered rows (image_span)
-    HostBuf h_out;           // stage of a pageable map (HostSpan)
-    int out_span = -1;       // index of this pair's output span in ws_context::batch_spans
-};
 
 thread_local std::string g_create_error; // ws_last_error(NULL): why the last ws_create on this thread failed
 
@@ -61,36 +49,6 @@ struct HostTrace {
 
 } // namespace
 
-struct ws_context {
-    int device = 0;
-    int num_cus = 256; // the device's (the consumers' grids; a copy in the Searcher plans the searches)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; // ws_timer_begin / ws_timer_end
-    Searcher searcher;                       // what only the searches touch (ws_search.h)
-    DevBuf d_left, d_right, d_out, d_out64 /* the consumers' scratch */, d_out16;
-    DevBuf d_rect_left, d_rect_right; // ws_search_unrectified_host: the rectified images
-    DevBuf d_mesh, d_mesh_text;       // the mesh text (ws_mesh.hip): per-workgroup sums / offsets and the file's bytes
-    HostBuf h_mesh[2];                // ... which come down through these two pinned chunks (kMeshChunk each)
-    hipEvent_t ev_mesh[2] = {};       // a chunk has landed in h_mesh[i]
-    Job jobs[2];             // ws_enqueue_host alternates between two slots
-    int job_next = 0;
-    hipStream_t copy_stream = nullptr; // host <-> device copies of the batched path, beside the searches
-    hipStream_t down_stream = nullptr; // ws_search_host in bands: maps go down here while images still come up on copy_stream
-    static constexpr int kMaxBands = 8;
-    hipEvent_t ev_band_up[kMaxBands] = {}, ev_band_done[kMaxBands] = {}, ev_band_down[kMaxBands] = {};
-    HostBuf status_page;               // 64 mapped pinned bytes: the words below
-    unsigned int *status_host = nullptr, *status_dev = nullptr; // mapped pinned words the kernels flag trouble in (word 0: ws_smooth_left_bands_kernel gave up; word 1: the integer box filter met a value it cannot carry)
-    DevBuf d_flag;                     // 256 bytes: word 0 = the integer box filter met a value it cannot carry
-    int last_outliers_path = 0;        // ws_last_outliers_path
-    int last_how[3] = {0, 0, 0};       // ws_last_host_paths: how the last host call's left / right / out bytes crossed
-    int last_wire = 0;                 // ... and the wire format of its map (ws_last_wire_format)
-    std::vector<HostSpan> batch_spans; // caller buffers of the pairs enqueued since the last ws_wait (released there)
-    HostBuf h_left, h_right, h_out;    // ws_search_host: stages (HostSpan), or gathered rows of cut-out images (image_span)
-    HostBuf h_aux[2];                  // stages of the consumers' further buffers
-    int host_bands = -1;               // ws_set_host_bands: 0 = never split, -1 = automatic
-    std::string err;
-};
-
 int wsamd::fail(std::string *err, int code, const char *fmt, ...)
 {
     char buf[512];
@@ -102,10 +60,7 @@ int wsamd::fail(std::string *err, int code, const char *fmt, ...)
     return code;
 }
 
-namespace {
-
-// What the kernels flagged since the last check (the streams that carried them are idle: the caller synchronised).
-int check_device_status(ws_context *ctx)
+int wsamd::check_device_status(ws_context *ctx)
 {
     if (!ctx->status_host || !ctx->status_host[0]) return WS_OK;
     ctx->status_host[0] = 0;
@@ -113,9 +68,7 @@ int check_device_status(ws_context *ctx)
                                        "(ws_smooth_left_bands_kernel): the map is not valid");
 }
 
-// The end of a synchronous host call: the streams idle (after an error too: nothing may still be copying when the spans are
-// released), staged downloads handed over -- or dropped if the call or a stream failed -- and a stream's error reported.
-int finish_host_call(ws_context *ctx, int rc, HostSpan *sp, int count, std::initializer_list<hipStream_t> streams, const char *what)
+int wsamd::finish_host_call(ws_context *ctx, int rc, HostSpan *sp, int count, std::initializer_list<hipStream_t> streams, const char *what)
 {
     hipError_t es = hipSuccess;
     for (hipStream_t s : streams) {
@@ -128,8 +81,6 @@ int finish_host_call(ws_context *ctx, int rc, HostSpan *sp, int count, std::init
     if (rc == WS_OK && es != hipSuccess) return fail(&ctx->err, WS_ERR_HIP, "%s: %s", what, hipGetErrorString(es));
     return rc;
 }
-
-} // namespace
 
 extern "C" {
 
@@ -214,6 +165,7 @@ void ws_destroy(ws_context *ctx)
             if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_mesh)
         if (e) (void)hipEventDestroy(e);
+    if (ctx->lr.ev) (void)hipEventDestroy(ctx->lr.ev);
     // every buffer goes with its owner, on this device, with nothing using it.  A batch never waited for: its maps are NOT
     // handed over -- only ws_wait delivers, and a caller who abandoned the batch may have freed the buffers they go to
     delete ctx;

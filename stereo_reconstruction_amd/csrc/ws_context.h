@@ -1,0 +1,88 @@
+// ws_context.h -- the context behind the C-ABI's opaque ws_context, for the sources that implement its entry points
+// (ws_capi.cpp, ws_lr.cpp), and the epilogue of their synchronous host calls.
+#pragma once
+
+#include "ws_capi_internal.h"
+#include "ws_search.h"
+#include "ws_staging.h"
+
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace wsamd {
+
+struct Job { // one pair in flight on the batched host path
+    DevBuf in;               // left image, then right image (rows with the caller's stride, or gathered dense)
+    DevBuf out, out16;       // the map as float32 / int16
+    int wire = 0;            // the wire format this pair's map comes down in
+    hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
+    void *user_out = nullptr;
+    int w = 0, h = 0, out_stride = 0, dtype = 0;
+    int row0 = 0;         // the first row of the device map that goes to user_out (a row band: its halo rows stay behind)
+    bool pending = false; // searched (or being searched), result not yet on its way to user_out
+    HostBuf h_left, h_right; // stages of the images, or their gathered rows (image_span)
+    HostBuf h_out;           // stage of a pageable map (HostSpan)
+    int out_span = -1;       // index of this pair's output span in ws_context::batch_spans
+};
+
+// The left-right check's device memory (ws_lr.cpp): the two raw maps of ws_search_lr_*, the per-pixel states the fill
+// reads, and the failure counters that ws_last_lr_counts reads.  Shared by every check of the context: a check on another
+// stream than the previous one first waits (on the device) for that one, as the Searcher's scratch planes do.
+struct LrState {
+    DevBuf raw;              // ws_search_lr_*: the left view's map, then the right view's (float32, dense)
+    DevBuf states;           // one byte per pixel of both maps (kLrEmpty / kLrPassed / kLrFailed)
+    DevBuf counts;           // the check kernel's failure counters (lr_slot_words()), then their sums: left map, right map
+    HostBuf counts_host;     // ... copied here behind the check kernel
+    hipEvent_t ev = nullptr; // end of the last check
+    hipStream_t stream = nullptr;
+    bool busy = false; // ev is recorded on `stream`
+    bool ran = false;  // a check was enqueued: counts_host holds (or will hold) its counts
+};
+
+} // namespace wsamd
+#pragma GCC visibility pop
+
+struct ws_context {
+    int device = 0;
+    int num_cus = 256; // the device's (the consumers' grids; a copy in the Searcher plans the searches)
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; // ws_timer_begin / ws_timer_end
+    wsamd::Searcher searcher;                       // what only the searches touch (ws_search.h)
+    wsamd::DevBuf d_left, d_right, d_out, d_out64 /* the consumers' scratch */, d_out16;
+    wsamd::DevBuf d_rect_left, d_rect_right; // ws_search_unrectified_host: the rectified images
+    wsamd::DevBuf d_mesh, d_mesh_text;       // the mesh text (ws_mesh.hip): per-workgroup sums / offsets and the file's bytes
+    wsamd::HostBuf h_mesh[2];                // ... which come down through these two pinned chunks (kMeshChunk each)
+    hipEvent_t ev_mesh[2] = {};       // a chunk has landed in h_mesh[i]
+    wsamd::Job jobs[2];             // ws_enqueue_host alternates between two slots
+    int job_next = 0;
+    hipStream_t copy_stream = nullptr; // host <-> device copies of the batched path, beside the searches
+    hipStream_t down_stream = nullptr; // ws_search_host in bands: maps go down here while images still come up on copy_stream
+    static constexpr int kMaxBands = 8;
+    hipEvent_t ev_band_up[kMaxBands] = {}, ev_band_done[kMaxBands] = {}, ev_band_down[kMaxBands] = {};
+    wsamd::HostBuf status_page;               // 64 mapped pinned bytes: the words below
+    unsigned int *status_host = nullptr, *status_dev = nullptr; // mapped pinned words the kernels flag trouble in (word 0: ws_smooth_left_bands_kernel gave up; word 1: the integer box filter met a value it cannot carry)
+    wsamd::DevBuf d_flag;                     // 256 bytes: word 0 = the integer box filter met a value it cannot carry
+    int last_outliers_path = 0;        // ws_last_outliers_path
+    int last_how[3] = {0, 0, 0};       // ws_last_host_paths: how the last host call's left / right / out bytes crossed
+    int last_wire = 0;                 // ... and the wire format of its map (ws_last_wire_format)
+    std::vector<wsamd::HostSpan> batch_spans; // caller buffers of the pairs enqueued since the last ws_wait (released there)
+    wsamd::HostBuf h_left, h_right, h_out;    // ws_search_host: stages (HostSpan), or gathered rows of cut-out images (image_span)
+    wsamd::HostBuf h_aux[2];                  // stages of the consumers' further buffers
+    int host_bands = -1;               // ws_set_host_bands: 0 = never split, -1 = automatic
+    wsamd::LrState lr;                        // the left-right check (ws_lr.cpp)
+    std::string err;
+};
+
+#pragma GCC visibility push(hidden)
+namespace wsamd {
+
+// What the kernels flagged since the last check (the streams that carried them are idle: the caller synchronised).
+int check_device_status(ws_context *ctx);
+// The end of a synchronous host call: the streams idle (after an error too: nothing may still be copying when the spans are
+// released), staged downloads handed over -- or dropped if the call or a stream failed -- and a stream's error reported.
+int finish_host_call(ws_context *ctx, int rc, HostSpan *sp, int count, std::initializer_list<hipStream_t> streams, const char *what);
+
+} // namespace wsamd
+#pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // ws_kernels.h -- launch interface between the C-ABI host code (ws_capi.cpp) and the
-// gfx950 kernels (ws_march / ws_prepass / ws_border / ws_smooth / ws_consumers / ws_mesh .hip).  Internal; the public boundary is include/ws_stereo.h.
+// gfx950 kernels (ws_march / ws_prepass / ws_border / ws_smooth / ws_consumers / ws_mesh / ws_lr .hip).  Internal; the public boundary is include/ws_stereo.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -149,4 +149,21 @@ hipError_t launch_mesh_write(const float *pos, const uint8_t *col, int w, int h,
 // bs_plane: w2 x h2 int16 (pitch bs_pitch), max_block: one device int (max grown block size)
 hipError_t launch_varblock(const GenericArgs &g, double thres, int16_t *bs_plane, int bs_pitch, int *max_block,
                            hipStream_t s);
+// Left-right consistency check (ws_lr.hip; the rules are in include/ws_stereo.h).  Map 0 is the left map (partner column
+// x - rint(v)), map 1 the right map (x + rint(v)); in/out pitches in elements.
+enum : uint8_t { kLrEmpty = 0, kLrPassed = 1, kLrFailed = 2 };
+struct LrMaps {
+    const float *in[2];
+    float *out[2];
+    int w[2], h[2], in_pitch[2], out_pitch[2];
+    uint8_t *state[2]; // one byte per pixel (pitch lr_state_pitch(w)), or null: the fill does not run
+};
+__host__ __device__ inline int lr_state_pitch(int w) { return (w + 3) & ~3; }
+// slots: lr_slot_words() counters, zero on entry (one 64-bit atomic per wave into one of kLrSlots per map); counts: 2
+// words, then the failed pixels of map 0 and of map 1
+constexpr int kLrSlots = 64, kLrSlotWords = 16; // counters 128 bytes apart
+constexpr size_t lr_slot_words() { return 2 * kLrSlots * kLrSlotWords; }
+hipError_t launch_lr_check(const LrMaps &m, float max_diff, unsigned long long *slots, unsigned long long *counts, hipStream_t s);
+// WS_LR_FILL_BACKGROUND: every failed pixel of the outputs from the nearest passed pixels of its row (states from the check)
+hipError_t launch_lr_fill(const LrMaps &m, hipStream_t s);
 } // namespace wsamd

@@ -145,6 +145,26 @@ public:
         return detail::run(device_, p, leftImage_, rightImage_);
     }
 
+    // Extension: computeDisparityMapLeft(smoothFactor) and computeDisparityMapRight(smoothFactor, varBlock, thres) in one
+    // call, then the left-right check (OpenCV's disp12MaxDiff = maxDiff; rules in ws_stereo.h).  {left map, right map}:
+    // a failed pixel is 0 (no disparity), or with fill the farther of the nearest passed pixels of its row.
+    std::pair<MatF64, MatF64> computeDisparityMapsChecked(double smoothFactor, float maxDiff = 1.0f, bool fill = false,
+                                                          bool varBlock = false, double thres = 19.0)
+    {
+        ws_params p = params(WS_VIEW_LEFT, smoothFactor);
+        p.var_block = varBlock;
+        p.thres = thres;
+        ws_lr_params lr;
+        lr.max_diff = maxDiff;
+        lr.fill = fill ? WS_LR_FILL_BACKGROUND : WS_LR_FILL_NONE;
+        std::pair<MatF64, MatF64> out(MatF64(leftImage_.rows, leftImage_.cols), MatF64(rightImage_.rows, rightImage_.cols));
+        const ws_image li = detail::to_c(leftImage_), ri = detail::to_c(rightImage_);
+        const int rc = ws_search_lr_host(device_.get(), &p, &li, &ri, &lr, out.first.ptr(), out.first.cols, out.second.ptr(),
+                                         out.second.cols, WS_OUT_F64);
+        if (rc != WS_OK) throw Error(rc, ws_last_error(device_.get()));
+        return out;
+    }
+
 private:
     ws_params params(int view, double smoothFactor) const
     {
