@@ -247,6 +247,37 @@ int ws_search_lr_device(ws_context *ctx, const ws_params *p, const ws_image *lef
 /* Pixels that failed in the last check of this context, {left, right}; waits for that check's stream. */
 int ws_last_lr_counts(ws_context *ctx, unsigned long long counts[2]);
 
+/* ---- speckle filter (extension) ----------------------------------------------------------- */
+/*
+ * OpenCV's filterSpeckles (calib3d/src/stereosgbm.cpp, filterSpecklesImpl) on a float32 map A, w x h, `stride` floats
+ * per row, in place:
+ *   1. A pixel is blank if A(y, x) == new_val (float ==: -0.0 is blank when new_val is 0).  Blank pixels belong to no
+ *      region and are left untouched, bits included.
+ *   2. Two 4-neighbours join if neither is blank and fabsf(a - b) <= max_diff, in float32: a NaN pixel joins nothing,
+ *      and +inf joins nothing unless max_diff is +inf (inf - finite then passes; inf - inf is NaN and never does).
+ *   3. A region is a connected component of the graph of those joins.
+ *   4. Every pixel of a region of count <= max_speckle_size pixels becomes exactly new_val; every other pixel keeps its
+ *      bits.  max_speckle_size == 0 changes nothing.
+ *   5. Counts: the pixels set to new_val, and the regions removed.
+ *   6. WS_ERR_ARG: new_val NaN; max_diff NaN or negative (+inf allowed); max_speckle_size < 0; a null pointer; w or h < 1;
+ *      stride < w; w * h >= 2^31.
+ * The rules do not depend on scan order.  On a map whose values, new_val and max_diff are integers in int16 range the
+ * result is OpenCV's CV_16SC1 result.  A filtered map with new_val 0 feeds ws_convert_disparity_to_depth as it is.
+ */
+typedef struct {
+    float new_val;        /* the value of blank pixels, and what removed pixels become */
+    int max_speckle_size; /* regions of at most this many pixels are removed */
+    float max_diff;       /* the largest |a - b| between 4-neighbours of one region */
+} ws_speckle_params;
+
+/* In place on a float32 map in device memory.  Only enqueues, on `stream` (NULL = the context's own). */
+int ws_filter_speckles_device(ws_context *ctx, float *map_dev, int w, int h, int stride, const ws_speckle_params *sp,
+                              void *stream);
+/* In place on a float32 map in host memory; synchronous. */
+int ws_filter_speckles_host(ws_context *ctx, float *map, int w, int h, int stride, const ws_speckle_params *sp);
+/* {pixels set to new_val, regions removed} by the last filter of this context; waits for that filter's stream. */
+int ws_last_speckle_counts(ws_context *ctx, unsigned long long counts[2]);
+
 /* ---- many pairs over the devices of a node ------------------------------------------------ */
 /*
  * Independent pairs are dealt to WORKERS: one ws_context and one host thread each.  Workers are device indices; a device

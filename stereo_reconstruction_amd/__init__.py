@@ -46,7 +46,8 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_pfm_read", "ws_pfm_write", "ws_free", "ws_ppm_read", "ws_ppm_write", "ws_calib_read", "ws_evaldisp",
            "ws_rectified_size", "ws_rectify_device", "ws_search_unrectified_host",
            "ws_batch_create", "ws_batch_destroy", "ws_batch_last_error", "ws_batch_workers", "ws_batch_plan",
-           "ws_batch_search_host", "ws_lr_check_device", "ws_search_lr_host", "ws_search_lr_device", "ws_last_lr_counts"]
+           "ws_batch_search_host", "ws_lr_check_device", "ws_search_lr_host", "ws_search_lr_device", "ws_last_lr_counts",
+           "ws_filter_speckles_device", "ws_filter_speckles_host", "ws_last_speckle_counts"]
 JOB_NOT_RUN = 1  # ws_job.status of a job its worker never reached (WS_JOB_NOT_RUN)
 
 
@@ -80,6 +81,16 @@ def lr_params(max_diff=1.0, fill=False):
     """ws_lr_params: the largest |v - partner| that passes the left-right check; fill=True fills failed pixels from
     the nearest passed pixels of their row (WS_LR_FILL_BACKGROUND), else they become 0."""
     return _LrParams(max_diff, LR_FILL_BACKGROUND if fill else LR_FILL_NONE)
+
+
+class _SpeckleParams(ctypes.Structure):
+    _fields_ = [("new_val", ctypes.c_float), ("max_speckle_size", ctypes.c_int), ("max_diff", ctypes.c_float)]
+
+
+def speckle_params(new_val=0.0, max_speckle_size=100, max_diff=1.0):
+    """ws_speckle_params: regions of at most max_speckle_size pixels whose 4-neighbours differ by at most max_diff
+    become new_val; pixels equal to new_val are blank (OpenCV's filterSpeckles)."""
+    return _SpeckleParams(new_val, max_speckle_size, max_diff)
 
 
 class _Job(ctypes.Structure):
@@ -199,6 +210,9 @@ def load_library(build_if_missing=False):
     lib.ws_search_lr_host.argtypes = [vp, P(_Params), P(_Image), P(_Image), P(_LrParams), vp, ci, vp, ci, ci]
     lib.ws_search_lr_device.argtypes = [vp, P(_Params), P(_Image), P(_Image), P(_LrParams), vp, ci, vp, ci, vp]
     lib.ws_last_lr_counts.argtypes = [vp, P(ctypes.c_ulonglong)]
+    lib.ws_filter_speckles_device.argtypes = [vp, vp, ci, ci, ci, P(_SpeckleParams), vp]
+    lib.ws_filter_speckles_host.argtypes = [vp, vp, ci, ci, ci, P(_SpeckleParams)]
+    lib.ws_last_speckle_counts.argtypes = [vp, P(ctypes.c_ulonglong)]
     _lib = lib
     return lib
 
@@ -354,6 +368,31 @@ class WindowSearch:
         """ws_last_lr_counts: (failed pixels of the left map, of the right map) in the last check of this context."""
         c = (ctypes.c_ulonglong * 2)()
         self._check(self._lib.ws_last_lr_counts(self._h, c))
+        return int(c[0]), int(c[1])
+
+    # -- speckle filter (extension; rules in include/ws_stereo.h) ---------------------------------
+    def filter_speckles(self, disparity, new_val=0.0, max_speckle_size=100, max_diff=1.0):
+        """ws_filter_speckles_host on a float32 copy of `disparity` (OpenCV's filterSpeckles); returns the copy."""
+        m = np.array(disparity, dtype=np.float32, order="C")
+        if m.ndim != 2:
+            raise ValueError("expected an H x W map")
+        sp = speckle_params(new_val, max_speckle_size, max_diff)
+        self._check(self._lib.ws_filter_speckles_host(self._h, m.ctypes.data, m.shape[1], m.shape[0], m.shape[1],
+                                                      ctypes.byref(sp)))
+        return m
+
+    def filter_speckles_device(self, t, new_val=0.0, max_speckle_size=100, max_diff=1.0, stream=None):
+        """ws_filter_speckles_device in place on a float32 CUDA map (H x W, rows may be padded).  Only enqueues."""
+        if t.dim() != 2 or t.stride(1) != 1 or t.element_size() != 4 or not t.is_floating_point():
+            raise ValueError("expected a float32 H x W tensor with dense rows")
+        sp = speckle_params(new_val, max_speckle_size, max_diff)
+        self._check(self._lib.ws_filter_speckles_device(self._h, t.data_ptr(), t.shape[1], t.shape[0], t.stride(0),
+                                                        ctypes.byref(sp), ctypes.c_void_p(stream or 0)))
+
+    def last_speckle_counts(self):
+        """ws_last_speckle_counts: (pixels set to new_val, regions removed) by the last filter of this context."""
+        c = (ctypes.c_ulonglong * 2)()
+        self._check(self._lib.ws_last_speckle_counts(self._h, c))
         return int(c[0]), int(c[1])
 
     def warp_nearest(self, src, matrix, dst_shape):

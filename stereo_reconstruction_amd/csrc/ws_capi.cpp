@@ -1,7 +1,7 @@
 // ws_capi.cpp -- the C-ABI of include/ws_stereo.h: the context, the entry points that run the search dispatch
 // (ws_search.h) on device memory or on the caller's host buffers (through ws_staging.h), and the rectify, consumer and
 // mesh calls.  Compiled with hipcc; no compute happens on the host.  The context is defined in ws_context.h; the
-// left-right check's entry points are in ws_lr.cpp.
+// left-right check's entry points are in ws_lr.cpp, the speckle filter's in ws_speckle.cpp.
 // The Middlebury plumbing (PFM, calib.txt, evaldisp) is in ws_io.cpp.
 #include "../../include/ws_stereo.h"
 #include "ws_kernels.h"
@@ -166,6 +166,7 @@ void ws_destroy(ws_context *ctx)
     for (hipEvent_t e : ctx->ev_mesh)
         if (e) (void)hipEventDestroy(e);
     if (ctx->lr.ev) (void)hipEventDestroy(ctx->lr.ev);
+    if (ctx->speckle.ev) (void)hipEventDestroy(ctx->speckle.ev);
     // every buffer goes with its owner, on this device, with nothing using it.  A batch never waited for: its maps are NOT
     // handed over -- only ws_wait delivers, and a caller who abandoned the batch may have freed the buffers they go to
     delete ctx;

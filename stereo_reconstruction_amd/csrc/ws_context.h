@@ -1,5 +1,5 @@
 // ws_context.h -- the context behind the C-ABI's opaque ws_context, for the sources that implement its entry points
-// (ws_capi.cpp, ws_lr.cpp), and the epilogue of their synchronous host calls.
+// (ws_capi.cpp, ws_lr.cpp, ws_speckle.cpp), and the epilogue of their synchronous host calls.
 #pragma once
 
 #include "ws_capi_internal.h"
@@ -41,6 +41,18 @@ struct LrState {
     bool ran = false;  // a check was enqueued: counts_host holds (or will hold) its counts
 };
 
+// The speckle filter's device memory (ws_speckle.cpp): the four int planes of the labelling, the counters, their sums on
+// the way to the host.  Shared by every filter of the context, with the same cross-stream wait as LrState.
+struct SpeckleState {
+    DevBuf planes;           // label, parent, count, local: w*h ints each (SpeckleArgs)
+    DevBuf counts;           // speckle_slot_words() counters, then their sums: pixels set, regions removed
+    HostBuf counts_host;     // ... copied here behind the filter
+    hipEvent_t ev = nullptr; // end of the last filter
+    hipStream_t stream = nullptr;
+    bool busy = false; // ev is recorded on `stream`
+    bool ran = false;  // a filter was enqueued: counts_host holds (or will hold) its counts
+};
+
 } // namespace wsamd
 #pragma GCC visibility pop
 
@@ -72,6 +84,7 @@ struct ws_context {
     wsamd::HostBuf h_aux[2];                  // stages of the consumers' further buffers
     int host_bands = -1;               // ws_set_host_bands: 0 = never split, -1 = automatic
     wsamd::LrState lr;                        // the left-right check (ws_lr.cpp)
+    wsamd::SpeckleState speckle;              // the speckle filter (ws_speckle.cpp)
     std::string err;
 };
 

@@ -1,5 +1,5 @@
 // ws_kernels.h -- launch interface between the C-ABI host code (ws_capi.cpp) and the
-// gfx950 kernels (ws_march / ws_prepass / ws_border / ws_smooth / ws_consumers / ws_mesh / ws_lr .hip).  Internal; the public boundary is include/ws_stereo.h.
+// gfx950 kernels (ws_march / ws_prepass / ws_border / ws_smooth / ws_consumers / ws_mesh / ws_lr / ws_speckle .hip).  Internal; the public boundary is include/ws_stereo.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -166,4 +166,20 @@ constexpr size_t lr_slot_words() { return 2 * kLrSlots * kLrSlotWords; }
 hipError_t launch_lr_check(const LrMaps &m, float max_diff, unsigned long long *slots, unsigned long long *counts, hipStream_t s);
 // WS_LR_FILL_BACKGROUND: every failed pixel of the outputs from the nearest passed pixels of its row (states from the check)
 hipError_t launch_lr_fill(const LrMaps &m, hipStream_t s);
+// Speckle filter (ws_speckle.hip; the rules are in include/ws_stereo.h).  The map is filtered in place.  The four int
+// planes hold w*h words each, indexed y*w + x (dense, whatever the map's stride): label = the index of the pixel's
+// tile-local root (-1: blank), and at local roots only: parent (union-find over local roots), count (the region's size at
+// its global root, or the whole size of a region that never leaves its tile) and local (the local size of a region that
+// crosses a tile edge, 0 for one that does not).  slots: speckle_slot_words() counters, zero on entry; counts: 2 words,
+// then the pixels set to new_val and the regions removed.
+struct SpeckleArgs {
+    float *map;
+    int w, h, stride;
+    float new_val, max_diff;
+    int max_size;
+    int *label, *parent, *count, *local;
+};
+constexpr int kSpeckleSlots = 64, kSpeckleSlotWords = 16; // counters 128 bytes apart (as the left-right check's)
+constexpr size_t speckle_slot_words() { return 2 * kSpeckleSlots * kSpeckleSlotWords; }
+hipError_t launch_speckle(const SpeckleArgs &a, unsigned long long *slots, unsigned long long *counts, hipStream_t s);
 } // namespace wsamd

@@ -380,6 +380,19 @@ inline void removeDisparityOutliers(MatF32 &disparityMap, int kernelSize, float 
     if (rc != WS_OK) throw Error(rc, ws_last_error(device.get()));
 }
 
+// Extension: cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) with OpenCV's argument order, on a float32 map in
+// place (rules in ws_stereo.h).  In the pipeline it goes after the search (or the left-right check), before
+// removeDisparityOutliers and the depth conversion.
+inline void filterSpeckles(MatF32 &img, double newVal, int maxSpeckleSize, double maxDiff, Device &device = Device::shared())
+{
+    ws_speckle_params sp;
+    sp.new_val = static_cast<float>(newVal);
+    sp.max_speckle_size = maxSpeckleSize;
+    sp.max_diff = static_cast<float>(maxDiff);
+    const int rc = ws_filter_speckles_host(device.get(), img.ptr(), img.cols, img.rows, img.cols, &sp);
+    if (rc != WS_OK) throw Error(rc, ws_last_error(device.get()));
+}
+
 inline MatF32 convertDisparityToDepth(const MatF32 &dispImage, float focalLength, float baseline,
                                       Device &device = Device::shared())
 {
