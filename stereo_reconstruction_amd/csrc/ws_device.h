@@ -109,6 +109,16 @@ __host__ __device__ constexpr bool ssd_needs_centring(int ww, int wh, int nd)
 {
     return 2LL * ww * wh * 3 * 255 * 255 * nd >= (1LL << 28);
 }
+// The v_sad_u32 chain of the SSD marching kernel (ws_march_kernel.h, march_sadp) keeps the tie tag in the bias operand:
+// one tag per bias register of a thread, x + nd - 1 of them, in ssd_sad_tag_bits bits below the cost.  It runs on plain
+// bytes only (its prefix sums must not decrease), for windows whose keys fit: per channel b^2 - 2ab = (b - a)^2 - a^2
+// lies in [-255^2, 255^2], so a key lies in [-255^2 n << t, (255^2 n << t) + 2^t - 1], n = ww * wh * 3 -- with 16 tags
+// 1.53 * 10^8 at 7 x 7 and 2.53 * 10^8 at 9 x 9, below 2^28.
+__host__ __device__ constexpr int ssd_sad_tag_bits(int x, int nd) { return ilog2c(2 * (x + nd - 1) - 1); }
+__host__ __device__ constexpr bool ssd_sad_chain(int ww, int wh, int x, int nd)
+{
+    return !ssd_needs_centring(ww, wh, nd) && ((255LL * 255 * ww * wh * 3 + 1) << ssd_sad_tag_bits(x, nd)) <= (long long)kValidKeyBound;
+}
 
 
 __device__ __forceinline__ uint32_t window_cost(const uint8_t *a, int sa, const uint8_t *b, int sb,

@@ -116,8 +116,10 @@ static double march_model_cost(const Canon &c, MarchShape sh)
 // squares -- stay inside (-2^28, 2^28) with nd tags per thread?  Per channel b^2 - 2ab = (b - a)^2 - a^2 lies in
 // [-255^2, 255^2] for plain bytes (bounded by 2 * 255^2 here, as ssd_needs_centring does) and in
 // [-128^2, 255^2 - 127^2] for centred ones (a = 127, b = -128 gives the top: a reference 255 against a target 0).
+// The v_sad_u32 chain's shapes (ssd_sad_chain) have X + nd - 1 tags and their own, exact bound.
 static bool ssd_key_fits(int ww, int wh, int nd)
 {
+    if (ssd_sad_chain(ww, wh, kX, nd)) return true;
     const long long per = ssd_needs_centring(ww, wh, nd) ? 255 * 255 - 127 * 127 : 2 * 255 * 255;
     return per * ww * wh * 3 * nd < (long long)kValidKeyBound;
 }
@@ -204,7 +206,7 @@ bool march_supported(const Canon &c)
     const int dcount = c.d_hi - c.d_lo + 1;
     if (dcount < 1) return false;
     // keys must stay inside (-2^28, 2^28)
-    //   SSD: (sum b^2 - 2 cross sum) << log2(ND) (ssd_key_fits)        SAD: window sum << tag bits
+    //   SSD: (sum b^2 - 2 cross sum) << tie-tag bits (ssd_key_fits)     SAD: window sum << tag bits
     if (!c.ssd && march_pk_window(c.ww, c.wh)) return dcount <= 65536; // packed SAD: 16-bit cost, 16-bit global tie tag
     if (c.ssd) return ssd_key_fits(c.ww, c.wh, march_nd(c));
     return (((long long)c.ww * c.wh * 3 * 255) << tag_bits_for(c)) < (long long)kValidKeyBound;

@@ -220,7 +220,7 @@ __device__ __forceinline__ uint32_t from_lane_plus(uint32_t v)
 }
 
 // One row entering (SIGN=+1) or leaving (SIGN=-1) the window of every (column, disparity) this
-// thread owns.
+// thread owns.  (SSD on plain bytes up to 9 x 9: march_sadp instead, whose keys carry the tag in the bias.)
 //   SAD: V = (window sum << shift) + global tie tag          key = V
 //   SSD: V = local tie tag - (2 * cross sum << LT)           key = bias[xb] + V
 //        (bias = box sum of the squared target pixels << LT, or poison for an invalid centre)
@@ -297,6 +297,8 @@ __device__ __forceinline__ void march_row(int32_t (&V)[X][ND], int32_t (&best)[X
 // left the strip so far into them: bias = (sum b^2 + 2 K E) << LT.  V and the bias wrap around in 32 bits by themselves,
 // their sum -- the key -- is exact.  One difference, one accumulate and one chain per step instead of two each:
 // 7.0 instead of 9.0 instructions per hypothesis in the steady state (+ X + WW - 1 v_not per thread and step).
+// (Kept for the windows march_sadp below does not take -- centred bytes, and 11 x 11 / 13 x 13 with 4 disparities per
+// thread, whose keys would not fit with its tags -- march_sadp runs everywhere else: 7 x 7 and 9 x 9 among them.)
 template <int X, int ND, int WW, bool CENTRED>
 __device__ __forceinline__ void march_fused_ssd(int32_t (&V)[X][ND], int32_t (&best)[X], const uint32_t (&pa)[X + WW - 1],
                                                 const uint32_t (&pb)[X + WW + ND - 2], const uint32_t (&qa)[X + WW - 1],
@@ -382,6 +384,121 @@ __device__ __forceinline__ void march_fused_ssd_halo(int32_t (&V)[X][ND], int32_
             const int32_t k1 = (int32_t)bi[x - j + ND - 2] + V[x][j + 1];
             // (spelled out: the compiler splits min(best, min(k0, k1)) into two v_min_i32 for a third of the columns; the
             // first pair of a step has nothing to compare with yet -- best[] enters as INT_MAX)
+            if (j == 0) best[x] = min(k0, k1);
+            else asm("v_min3_i32 %0, %1, %2, %3" : "=v"(best[x]) : "v"(best[x]), "v"(k0), "v"(k1));
+        }
+    }
+}
+
+// ---- SSD with unshifted window sums: one v_sad_u32 per window update (plain bytes, ssd_sad_chain) ----------------
+// The same fused chain with the complement moved to the ENTERING row: (255 - a) . b for the row that enters, a . b for
+// the one that leaves.  Every v_dot4_u32_u8 then adds a nonnegative amount, so a step's prefix S never decreases nor
+// wraps (it stays below 2 * (X + WW - 1) * 3 * 255^2 < 2^23), and a window's value S[x + WW - 1] - S[x - 1] is
+// nonnegative: one v_sad_u32 (|hi - lo| + acc) adds it to the running sum P.  P telescopes to
+//     P = -(cross sum) + 255 E          (E: sum of the target bytes over the window's columns, every row entered so far)
+// and the key is  (P << (KT + 1)) + bias'  -- one v_lshl_add_u32 -- with  bias' = (sum b^2 - 510 E) << KT + tie tag,
+// the same key modulo 2^32 as the shifted chain's.  P holds no tag (its low bits are shifted out), so the tag goes into
+// the bias operand: for an output column x, bias register k = x - j + ND - 1 is one to one with the disparity j, and
+// tag (X + ND - 2 - k) orders a thread's candidates of one column as j does (for prefer_large its XOR with 2^KT - 1,
+// k + 2^KT - (X + ND - 1), as ND - 1 - j does).  KT = ssd_sad_tag_bits(X, ND) bits: 4 at 8 x 8 and 8 x 4.  Per hypothesis in the steady state:
+// 3.5 v_dot4 + 1 v_sad_u32 + 1 v_lshl_add + 0.5 v_min3 (+ 15 tag additions per thread and step), against 3.5 + 1 v_sub
+// + 1 v_lshl_add + 1 v_add + 0.5 v_min3; a row of the warm-up 2.75 instead of 3.75.
+__device__ __forceinline__ uint32_t sad_u32(uint32_t hi, uint32_t lo, uint32_t acc)
+{
+    return max(hi, lo) - min(hi, lo) + acc; // (the compiler's pattern for v_sad_u32)
+}
+
+// bi[k] += (N - 1 - k) ^ tmask: the tie tags of march_sadp, one v_xad_u32 each (tmask: a scalar, 0 or 2^KT - 1)
+template <int N, int K = 0>
+__device__ __forceinline__ void sadp_tags(uint32_t (&bi)[N], uint32_t tmask)
+{
+    if constexpr (K < N) {
+        asm("v_xad_u32 %0, %1, %2, %3" : "=v"(bi[K]) : "n"(N - 1 - K), "s"(tmask), "v"(bi[K]));
+        sadp_tags<N, K + 1>(bi, tmask);
+    }
+}
+
+// One step of the chain: the row entering (ca: its reference pixels complemented) and, LEAVE, the row leaving (la:
+// plain) of every (column, disparity) this thread owns; KEY: the candidate keys into best[] (bt: bias' + tag).
+template <int X, int ND, int WW, bool LEAVE, bool KEY>
+__device__ __forceinline__ void march_sadp(int32_t (&P)[X][ND], int32_t (&best)[X], const uint32_t (&ca)[X + WW - 1],
+                                           const uint32_t (&pb)[X + WW + ND - 2], const uint32_t (&la)[X + WW - 1],
+                                           const uint32_t (&qb)[X + WW + ND - 2], const uint32_t (&bt)[X + ND - 1])
+{
+    constexpr int NA = X + WW - 1, KT = ssd_sad_tag_bits(X, ND);
+#pragma unroll
+    for (int j = 0; j < ND; j += 2) {
+        uint32_t S0[NA], S1[NA];
+        uint32_t s0 = 0, s1 = 0;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            s0 = pix_dot<false>(ca[i], pb[i - j + ND - 1], s0);
+            s1 = pix_dot<false>(ca[i], pb[i - j + ND - 2], s1);
+            if constexpr (LEAVE) {
+                s0 = pix_dot<false>(la[i], qb[i - j + ND - 1], s0);
+                s1 = pix_dot<false>(la[i], qb[i - j + ND - 2], s1);
+            }
+            S0[i] = s0;
+            S1[i] = s1;
+        }
+#pragma unroll
+        for (int x = 0; x < X; ++x) {
+            const uint32_t p0 = x ? sad_u32(S0[x + WW - 1], S0[x - 1], (uint32_t)P[x][j]) : S0[WW - 1] + (uint32_t)P[x][j];
+            const uint32_t p1 = x ? sad_u32(S1[x + WW - 1], S1[x - 1], (uint32_t)P[x][j + 1]) : S1[WW - 1] + (uint32_t)P[x][j + 1];
+            P[x][j] = (int32_t)p0;
+            P[x][j + 1] = (int32_t)p1;
+            if constexpr (KEY) {
+                const int32_t k0 = (int32_t)((p0 << (KT + 1)) + bt[x - j + ND - 1]); // v_lshl_add_u32
+                const int32_t k1 = (int32_t)((p1 << (KT + 1)) + bt[x - j + ND - 2]);
+                // (spelled out as in march_fused_ssd)
+                if (j == 0) best[x] = min(k0, k1);
+                else asm("v_min3_i32 %0, %1, %2, %3" : "=v"(best[x]) : "v"(best[x]), "v"(k0), "v"(k1));
+            }
+        }
+    }
+}
+
+// The steady state of march_sadp with the window's right-hand part from the neighbouring thread (march_fused_ssd_halo):
+// T = S[X-1] + N[x + WW - 1 - X] (v_add_u32_dpp), then v_sad_u32(T, S[x-1], P) -- two instructions where the shifted
+// chain spends two subtractions and a v_lshl_add.
+template <int X, int ND, int WW>
+__device__ __forceinline__ void march_sadp_halo(int32_t (&P)[X][ND], int32_t (&best)[X], const uint32_t (&ca)[X],
+                                                const uint32_t (&pb)[X + ND - 1], const uint32_t (&la)[X],
+                                                const uint32_t (&qb)[X + ND - 1], const uint32_t (&bt)[X + ND - 1])
+{
+    static_assert(WW - 1 <= X && WW >= 2, "the next run covers the whole overhang of a window");
+    constexpr int KT = ssd_sad_tag_bits(X, ND);
+#pragma unroll
+    for (int j = 0; j < ND; j += 2) {
+        uint32_t S0[X], S1[X];
+        uint32_t s0 = 0, s1 = 0;
+#pragma unroll
+        for (int i = 0; i < X; ++i) {
+            s0 = pix_dot<false>(ca[i], pb[i - j + ND - 1], s0);
+            s1 = pix_dot<false>(ca[i], pb[i - j + ND - 2], s1);
+            s0 = pix_dot<false>(la[i], qb[i - j + ND - 1], s0);
+            s1 = pix_dot<false>(la[i], qb[i - j + ND - 2], s1);
+            S0[i] = s0;
+            S1[i] = s1;
+        }
+#pragma unroll
+        for (int x = 0; x < X; ++x) {
+            constexpr int kLastInside = X - WW; // the last column whose window ends inside the thread's own columns
+            uint32_t hi0, hi1;
+            if (x <= kLastInside) {
+                hi0 = S0[x <= kLastInside ? x + WW - 1 : 0];
+                hi1 = S1[x <= kLastInside ? x + WW - 1 : 0];
+            } else {
+                const int m = x + WW - 1 - X; // the next run's prefix that completes this window
+                hi0 = S0[X - 1] + from_next_lane(S0[m]);
+                hi1 = S1[X - 1] + from_next_lane(S1[m]);
+            }
+            const uint32_t p0 = x ? sad_u32(hi0, S0[x - 1], (uint32_t)P[x][j]) : hi0 + (uint32_t)P[x][j];
+            const uint32_t p1 = x ? sad_u32(hi1, S1[x - 1], (uint32_t)P[x][j + 1]) : hi1 + (uint32_t)P[x][j + 1];
+            P[x][j] = (int32_t)p0;
+            P[x][j + 1] = (int32_t)p1;
+            const int32_t k0 = (int32_t)((p0 << (KT + 1)) + bt[x - j + ND - 1]);
+            const int32_t k1 = (int32_t)((p1 << (KT + 1)) + bt[x - j + ND - 2]);
             if (j == 0) best[x] = min(k0, k1);
             else asm("v_min3_i32 %0, %1, %2, %3" : "=v"(best[x]) : "v"(best[x]), "v"(k0), "v"(k1));
         }
@@ -589,6 +706,9 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
     constexpr int NREG = X / 4, NREGB = march_nreg_b(X, ND);
     constexpr int LT = ilog2c(ND);
     constexpr bool CENTRED = SSD && ssd_needs_centring(WW, WH, ND);
+    // SSD on plain bytes where the keys fit: the v_sad_u32 chain (march_sadp), keys (cost << KT) + tag, the tag in the bias
+    constexpr bool SADP = SSD && kFuseSsd && ssd_sad_chain(WW, WH, X, ND);
+    constexpr int KT = SADP ? ssd_sad_tag_bits(X, ND) : LT; // tie-tag bits below an SSD key's cost
     constexpr int NR = WH + 2; // ring rows: WH+1 in use by a step, 1 being unpacked for the next
     // merge slots: SSD (cost << LT | 7) : global tie tag as one signed 64-bit key, SAD the 32-bit key itself;
     // a key at or above kValidKeyBound (in its cost word) is "no valid candidate"
@@ -678,6 +798,11 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
     // SSD merge: global tie tag = chunk tag | local tag (a multiple of ND, so one v_and_or builds it):
     // the chunk's distance from the preferred end of the padded range [d_lo, d_top]
     const int ctag = g.prefer_large ? g.d_top - d0 - (ND - 1) : d0 - g.d_lo;
+    // SADP: the slot's tag word is (ctag / ND) : the bias tag, KT bits -- the global tag's order for the candidates of one
+    // slot (the bias tag minus an offset that depends on the column inside the thread alone is the local tag), decoded
+    // by the flush
+    const uint32_t ctag_hi = (uint32_t)ctag << (KT - LT);
+    const uint32_t tmask = SADP && g.prefer_large ? (1u << KT) - 1u : 0u; // march_sadp's tags: (X + ND - 2 - k) ^ tmask
 
     int32_t V[PK ? 1 : X][PK ? 1 : ND];
     uint32_t Vp[PK ? X : 1][PK ? ND / 2 : 1], tagr[PK ? ND : 1];
@@ -715,7 +840,12 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
 #pragma unroll
         for (int j = 0; j < ND; ++j) {
             const int d = d0 + j;
-            if constexpr (SSD) {
+            if constexpr (SADP) {
+                // P holds no tag; a disparity beyond d_hi is poisoned through it (kPoison once shifted into the key)
+                static_assert(kPoison % (1 << (KT + 1)) == 0, "the poison survives the shift");
+#pragma unroll
+                for (int x = 0; x < X; ++x) V[x][j] = d <= g.d_hi ? 0 : kPoison >> (KT + 1);
+            } else if constexpr (SSD) {
                 // local tag: the preferred disparity of a tie gets the smaller tag
                 const int tag = g.prefer_large ? (ND - 1 - j) : j;
                 const int32_t init = (d <= g.d_hi) ? tag : (kPoison + tag);
@@ -867,11 +997,20 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
                         // column sums: row iu enters, row iu - WH leaves and joins the correction term.  Plain bytes: with
                         // x = 255 - b per channel, -b^2 + 510 b = 3 * 255^2 - x.x, so the sums are kept WITHOUT the constant
                         // (G'' = G - 3 * 255^2 * rows left so far) and a leaving pixel costs an xor, a dot and a subtraction;
-                        // the bias values get WW times the constant back below
+                        // the bias values get WW times the constant back below.  SADP (march_sadp): the correction is
+                        // -510 b for every row that ENTERS, b^2 - 510 b = x.x - 3 * 255^2, so an entering pixel costs the xor
+                        // and a leaving one a plain dot; the bias values lose WW times the constant per row entered so far
                         const uint4 gp = lds_load128(lds0 + d.z + (par ^ 1u) * (uint32_t)kGB);
                         uint32_t gn[4] = {gp.x, gp.y, gp.z, gp.w};
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) gn[e] = pix_dot<CENTRED>(px[e], px[e], gn[e]);
+                        for (int e = 0; e < 4; ++e) {
+                            if constexpr (SADP) {
+                                const uint32_t xc = px[e] ^ 0x00ffffffu;
+                                gn[e] = pix_dot<false>(xc, xc, gn[e]);
+                            } else {
+                                gn[e] = pix_dot<CENTRED>(px[e], px[e], gn[e]);
+                            }
+                        }
                         if (iu >= WH) {
                             int slot_l = slot_u + 2; // row iu - WH
                             if (slot_l >= NR) slot_l -= NR;
@@ -879,7 +1018,9 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
                             const uint32_t lp[4] = {lv.x, lv.y, lv.z, lv.w};
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                if constexpr (kMul == 510) {
+                                if constexpr (SADP) {
+                                    gn[e] -= pix_dot<false>(lp[e], lp[e], 0u);
+                                } else if constexpr (kMul == 510) {
                                     const uint32_t xc = lp[e] ^ 0x00ffffffu;
                                     gn[e] -= pix_dot<false>(xc, xc, 0u);
                                 } else {
@@ -905,10 +1046,12 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
                                 else v = from_lane_plus<5>(gn[m & 3]);
                                 pre[m] = pre[m - 1] + v;
                             }
-                            const uint32_t cst = kMul == 510 ? ((uint32_t)(WW * 3 * 255 * 255) * (uint32_t)max(0, iu - WH + 1)) << LT : 0u;
+                            const uint32_t cst = SADP           ? (0u - (uint32_t)(WW * 3 * 255 * 255) * (uint32_t)(iu + 1)) << KT
+                                                 : kMul == 510 ? ((uint32_t)(WW * 3 * 255 * 255) * (uint32_t)max(0, iu - WH + 1)) << LT
+                                                               : 0u;
                             uint32_t o[4];
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) o[e] = ((pre[e + WW - 1] - (e ? pre[e - 1] : 0u)) << LT) + cst;
+                            for (int e = 0; e < 4; ++e) o[e] = ((pre[e + WW - 1] - (e ? pre[e - 1] : 0u)) << KT) + cst;
                             if (sflags & 4u) { // (uniform: a tile with target centres outside [b_lo, b_hi]: their keys are poisoned)
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) o[e] += __builtin_amdgcn_ubfe(d.w, 12 + e, 1) << 29;
@@ -987,7 +1130,9 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
                 if (none) {
                     val = g.fallback_neg ? -(float)xo : (float)xo;
                 } else {
-                    const int gtag = SSD ? (int)(uint32_t)key : PK ? (int)((uint32_t)key & 0xffffu) : ((int)key & ((1 << g.tag_bits) - 1));
+                    int gtag = SSD ? (int)(uint32_t)key : PK ? (int)((uint32_t)key & 0xffffu) : ((int)key & ((1 << g.tag_bits) - 1));
+                    if constexpr (SADP) // (ctag_hi; the bias tag's offset for this column inside the thread)
+                        gtag = ((gtag >> KT) << LT) + (gtag & ((1 << KT) - 1)) - (g.prefer_large ? k % X + (1 << KT) - (X + ND - 1) : X - 1 - k % X);
                     val = (float)(g.prefer_large ? (SSD ? g.d_top : g.d_hi) - gtag : g.d_lo + gtag);
                 }
                 // black pixel (BlockSearch.cpp:41, :105): image row y, column x, from the ring
@@ -996,7 +1141,7 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
                 else g.out[(size_t)y * g.out_pitch + xo] = val;
                 if (COST && !none) { // (a template flag: the test alone cost the hot kernel 2.7 %)
                     int32_t cst;
-                    if constexpr (SSD) cst = (int32_t)((long long)key >> 32) >> LT;
+                    if constexpr (SSD) cst = (int32_t)((long long)key >> 32) >> KT;
                     else if constexpr (PK) cst = (int32_t)((uint32_t)key >> 16);
                     else cst = (int32_t)key >> g.tag_bits;
                     g.cost_out[(size_t)y * g.cost_pitch + xo] = cst;
@@ -1050,7 +1195,24 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
 #pragma unroll
                 for (int x = 0; x < X; ++x) best[x] = INT_MAX;
                 const int32_t *brow = biasr + (oi & 1) * bi_w + ib;
-                if constexpr (PHASE == 0) {
+                if constexpr (SADP) {
+                    // row a enters (reference pixels complemented, from the twin of ring A); PHASE 2: row a - WH leaves
+                    constexpr int NPA = HALO && PHASE == 2 ? X : X + WW - 1, NPB = NPA + ND - 1;
+                    const uint32_t *addAc = ringAc + add_slot * a_w + ia;
+                    uint32_t ca[NPA], pb[NPB], la[NPA], qb[NPB], bt[X + ND - 1];
+                    lds_run<NPA, NREG>(ca, addAc, ro_a);
+                    lds_run<NPB, NREGB>(pb, addB, ro_b);
+                    if constexpr (PHASE >= 1) {
+                        lds_run<X + ND - 1, NREGB>(bt, reinterpret_cast<const uint32_t *>(brow), ro_bi);
+                        sadp_tags(bt, tmask);
+                    }
+                    if constexpr (PHASE == 2) {
+                        lds_run<NPA, NREG>(la, subA, ro_a);
+                        lds_run<NPB, NREGB>(qb, subB, ro_b);
+                    }
+                    if constexpr (PHASE == 2 && HALO) march_sadp_halo<X, ND, WW>(V, best, ca, pb, la, qb, bt);
+                    else march_sadp<X, ND, WW, PHASE == 2, PHASE >= 1>(V, best, ca, pb, la, qb, bt);
+                } else if constexpr (PHASE == 0) {
                     march_row<X, ND, WW, SSD, CENTRED, +1, false>(V, best, addA, ro_a, addB, ro_b, nullptr, 0, shift);
                 } else if constexpr (PHASE == 1) {
                     march_row<X, ND, WW, SSD, CENTRED, +1, true>(V, best, addA, ro_a, addB, ro_b, brow, ro_bi, shift);
@@ -1080,7 +1242,13 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
                     for (int x = 0; x < X; ++x) {
                         const int32_t bk = best[x];
                         // no validity test here: a poisoned key is just a large one, the flush sorts it out
-                        if constexpr (SSD) {
+                        if constexpr (SADP) {
+                            // cost word: the key without its tag; tag word: the chunk's tag above the bias tag (v_and_or_b32)
+                            const uint32_t hi = (uint32_t)bk & ~((1u << KT) - 1u);
+                            const uint32_t lo = ((uint32_t)bk & ((1u << KT) - 1u)) | ctag_hi;
+                            const long long key = (long long)(((unsigned long long)hi << 32) | lo);
+                            atomicMin(reinterpret_cast<long long *>(sl) + x * g.st.nxr, key);
+                        } else if constexpr (SSD) {
                             const uint32_t gtag = (uint32_t)(bk & (ND - 1)) | (uint32_t)ctag; // v_and_or_b32
                             const long long key = (long long)(((unsigned long long)(uint32_t)(bk | (ND - 1)) << 32) | gtag);
                             atomicMin(reinterpret_cast<long long *>(sl) + x * g.st.nxr, key); // ds_min_i64, lanes on consecutive slots

@@ -42,6 +42,12 @@ __global__ void __launch_bounds__(256) k(uint32_t *out, int iters, uint32_t seed
                 if (OP == 11) acc[c] = __builtin_amdgcn_perm(acc[c], a, 0x05040100u + c); // v_perm_b32
                 if (OP == 12) acc[c] = (acc[c] & 0xffffffu) * (a & 0xffffffu) + b; // v_mad_u32_u24
                 if (OP == 13) acc[c] = __builtin_amdgcn_udot4(a, b + c, acc[c], false) - a;   // dot4 + dependent sub
+                // v_sad_u32 (|x - y| + acc: the SSD chain's window update, ws_march_kernel.h march_sadp)
+                if (OP == 14) asm volatile("v_sad_u32 %0, %1, %2, %0" : "+v"(acc[c]) : "v"(acc[(c + 1) % CHAINS]), "v"(a));
+                if (OP == 15) { // v_add_u32_dpp (row_shl:1) + v_sad_u32: the halo-exchange form (march_sadp_halo)
+                    const uint32_t t = (uint32_t)__builtin_amdgcn_mov_dpp((int)acc[(c + 1) % CHAINS], 0x101, 0xf, 0xf, true) + a;
+                    asm volatile("v_sad_u32 %0, %1, %2, %0" : "+v"(acc[c]) : "v"(t), "v"(b));
+                }
             }
         }
     }
@@ -111,7 +117,7 @@ void run(const char *name, int waves_per_simd)
 {
     const int blocks = 256 * waves_per_simd; // 256-thread blocks = 4 waves = 1 per SIMD per block
     const float ms = time_ms([&](int iters) { hipLaunchKernelGGL((k<OP, CHAINS>), dim3(blocks), dim3(256), 0, 0, g_d, iters, 1u); });
-    const double insts_per_simd = 4000.0 * 16 * CHAINS * waves_per_simd * ((OP == 3 || OP == 13 || OP == 6 || OP == 10) ? 2 : 1);
+    const double insts_per_simd = 4000.0 * 16 * CHAINS * waves_per_simd * ((OP == 3 || OP == 13 || OP == 6 || OP == 10 || OP == 15) ? 2 : 1);
     const double cyc = ms * 1e-3 * 2.4e9;
     printf("%-14s chains=%d waves/SIMD=%d : %8.3f ms -> %5.2f cycles(@2.4GHz)/wave-instr/SIMD, %6.2f Tlane-op/s\n", name, CHAINS,
            waves_per_simd, ms, cyc / insts_per_simd, insts_per_simd * 1024 * 64 / (ms * 1e-3) / 1e12);
@@ -142,6 +148,8 @@ int main()
         run<2, 4>("lshl_add", w);
         run<3, 4>("min+add", w);
         run<4, 4>("sub", w);
+        run<14, 4>("sad_u32", w);
+        run<15, 4>("add_dpp+sad_u32", w);
         run<6, 4>("xor+min3", w);
         run<7, 4>("add3", w);
         run<9, 4>("pk_add_u16", w);
