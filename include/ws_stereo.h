@@ -78,7 +78,10 @@ typedef struct {
     int max_disparity;    /* maxDisparity: left tries d = maxD..1, right d = minD..maxD-1 */
     double smooth_factor; /* smoothFactor, any value but NaN (!= 1 in the left view is a true raster-order
                              dependency, SURVEY.md 8f-1: a serial pass of a few ms) */
-    int var_block;        /* varBlock (right view): grow the window while its centred norm < thres */
+    int var_block;        /* varBlock (right view): grow the window (block size + 4) while its centred norm < thres;
+                             growth stops when the clipped window no longer changes (the reference would loop
+                             forever there), and the max block counts that last + 4.  A grown window is not bound
+                             by block_size's limit of 63: it can span the whole image (costs summed in 64 bits) */
     double thres;         /* thres for varBlock, default 19.0 (BlockSearch.h:37) */
     int subpixel;         /* extension: parabolic refinement on the aggregated integer cost */
     int linear_range;     /* LinearSearch's hard-coded 200 candidates (LinearSearch.cpp:32) */

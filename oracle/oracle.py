@@ -10,7 +10,7 @@ The functions mirror the reference's call surface:
   linear       ~ LinearSearch(L,R).computeDisparityMap(s)                    (LinearSearch.cpp:10-59)
   evaldisp     ~ evaldisp(disp, gt, mask, badthresh, maxdisp, rounddisp)     (utils.cpp:123-168)
   fast_left / fast_right: block_left / block_right bit for bit, in O(H * W * D) whatever the window
-    size (oracle/ws_fast.c): whole full-size maps in seconds; no var_block
+    size (oracle/ws_fast.c): whole full-size maps in seconds, var_block included (fast_right thres=, return_max_block=)
   subpixel: False, True (the parabolic refinement in double) or "float32" (rounded as the device rounds it)
 Images are H x W x 3 uint8 arrays (BGR), outputs float64 maps.
 """
@@ -112,6 +112,9 @@ def lib():
             ctypes.c_double] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         _lib.wsf_block_right.argtypes = [P(_Image), P(_Image)] + [ctypes.c_int] * 3 + [
             ctypes.c_double] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        _lib.wsf_block_right_vb.argtypes = [P(_Image), P(_Image)] + [ctypes.c_int] * 3 + [
+            ctypes.c_double, ctypes.c_int, ctypes.c_double] + [ctypes.c_int] * 4 + [
+            ctypes.c_void_p, ctypes.c_int, P(ctypes.c_int), ctypes.c_int]
         _lib.wso_evaldisp.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [
             ctypes.c_float, ctypes.c_float, ctypes.c_int, P(ctypes.c_double)]
     return _lib
@@ -128,8 +131,8 @@ def _check(rc):
     if rc == -2:
         raise OracleGeometryError("reference would throw cv::Exception (ROI outside image)")
     if rc == -4:
-        raise NotImplementedError("the fast reference does not implement these arguments (var_block, or window "
-                                  "sums past 32 bits)")
+        raise NotImplementedError("the fast reference does not implement these arguments (var_block with sub-pixel, "
+                                  "or window sums past 32 bits)")
     if rc != 0:
         raise ValueError("oracle rejected the arguments (code %d)" % rc)
 
@@ -198,17 +201,20 @@ def fast_left(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
 
 
 def fast_right(L, R, block_size, min_disparity, max_disparity, smooth=1.0,
-               var_block=False, cost="ssd", subpixel=False, rows=None, threads=0):
-    """block_right's map, computed by the fast reference; var_block raises NotImplementedError."""
+               var_block=False, cost="ssd", subpixel=False, rows=None, threads=0, thres=19.0,
+               return_max_block=False):
+    """block_right's map (and max block size), computed by the fast reference; var_block together with subpixel
+    raises NotImplementedError."""
     La, Li = _img(L)
     Ra, Ri = _img(R)
     out = np.zeros((Ra.shape[0], Ra.shape[1]), dtype=np.float64)
     y0, y1 = _rows(rows, Ra.shape[0])
-    _check(lib().wsf_block_right(ctypes.byref(Li), ctypes.byref(Ri), block_size,
-                                 min_disparity, max_disparity, smooth, int(var_block),
-                                 COST[cost], _subpixel(subpixel), y0, y1,
-                                 out.ctypes.data, out.shape[1], int(threads or host_threads())))
-    return out
+    mb = ctypes.c_int(0)
+    _check(lib().wsf_block_right_vb(ctypes.byref(Li), ctypes.byref(Ri), block_size,
+                                    min_disparity, max_disparity, smooth, int(var_block), float(thres),
+                                    COST[cost], _subpixel(subpixel), y0, y1,
+                                    out.ctypes.data, out.shape[1], ctypes.byref(mb), int(threads or host_threads())))
+    return (out, mb.value) if return_max_block else out
 
 
 def linear(L, R, smooth=1.0, search_range=200, rows=None, threads=1):

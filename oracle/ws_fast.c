@@ -527,15 +527,347 @@ int wsf_block_left(const wso_image *L, const wso_image *R, int block_size,
                          : search_smooth(&g, smooth, ya, yb, out, out_stride, threads);
 }
 
-int wsf_block_right(const wso_image *L, const wso_image *R, int block_size,
-                    int min_disparity, int max_disparity, double smooth,
-                    int var_block, int cost, int subpixel, int y0, int y1,
-                    double *out, int out_stride, int threads)
+/* ---- varBlock (BlockSearch.cpp:125-145): every right-view pixel its own window -------------------------------
+ *
+ * A route of its own, all sums 64-bit:
+ *   texture  the window's per-channel value histogram, extended by the pixels a growth step adds (a window only
+ *            grows), gives the exact integer channel sums (the mean) and the centred norm as sum over v of
+ *            count[v] * clamp(rint((float)v - (float)mean))^2 -- the float32 subtraction depends on v alone;
+ *            small windows are scanned directly instead
+ *   costs    per disparity one summed-area table of the pixel cost over the right image's grid; a window's cost
+ *            is four reads of it, whatever the window, O(H * W * D) in all
+ *   decision smooth == 1: the first minimum of the integer costs in d order (sqrt and / area are strictly
+ *            increasing over the sums that occur, checked below); smooth != 1: the raster pass with the
+ *            reference's doubles -- the factor only reaches a d with -d equal to a neighbour's stored value, at
+ *            most two per pixel, so the three best (cost, d) per pixel and the costs at those d decide it. */
+
+typedef struct {
+    int l, r, u, dn;           /* window extents about (x, y): columns [x - l, x + r), rows [y - u, y + dn) */
+} vb_win;
+
+/* the three best (cost, d) in lexicographic order; n of them valid */
+typedef struct {
+    uint64_t c[3];
+    int d[3];
+    int n;
+} vb_top;
+
+static inline void vb_clip(int w2, int h2, int x, int y, int bs, vb_win *w)
+{
+    const int hb = (bs - 1) / 2;
+    w->l = x < hb ? x : hb;
+    w->r = w2 - x - 1 < hb ? w2 - x - 1 : hb;
+    w->u = y < hb ? y : hb;
+    w->dn = h2 - y - 1 < hb ? h2 - y - 1 : hb;
+}
+
+typedef struct {
+    int64_t hist[3][256];
+    int64_t sum[3];
+    int on;                    /* the histogram holds the window */
+} vb_hist;
+
+static void vb_hist_add(vb_hist *h, const wso_image *R, int xa, int xb, int ya, int yb)
+{
+    for (int y = ya; y < yb; ++y) {
+        const uint8_t *p = pix(R, y, xa);
+        for (int i = 0; i < xb - xa; ++i)
+            for (int c = 0; c < 3; ++c) {
+                h->hist[c][p[3 * i + c]]++;
+                h->sum[c] += p[3 * i + c];
+            }
+    }
+}
+
+static inline int64_t vb_sq(float v, float fm)
+{
+    float fd = v - fm;
+    long t = lrintf(fd);
+    if (t < 0) t = 0;
+    if (t > 255) t = 255;
+    return (int64_t)(t * t);
+}
+
+/* cv::norm(window - cv::mean(window)) of w about (x, y), as wso_centred_norm defines it (ws_oracle.h). */
+static double vb_texture(const wso_image *R, int x, int y, const vb_win *w, const vb_win *prev, vb_hist *h)
+{
+    const int ww = w->l + w->r, wh = w->u + w->dn;
+    if (ww <= 0 || wh <= 0) return 0.0;
+    const double n = (double)ww * (double)wh;
+    if (ww * wh <= 96) {       /* small window: two direct passes */
+        int64_t s[3] = {0, 0, 0};
+        for (int yy = y - w->u; yy < y + w->dn; ++yy) {
+            const uint8_t *p = pix(R, yy, x - w->l);
+            for (int i = 0; i < ww; ++i)
+                for (int c = 0; c < 3; ++c) s[c] += p[3 * i + c];
+        }
+        float fm[3];
+        for (int c = 0; c < 3; ++c) fm[c] = (float)((double)s[c] / n);
+        int64_t acc = 0;
+        for (int yy = y - w->u; yy < y + w->dn; ++yy) {
+            const uint8_t *p = pix(R, yy, x - w->l);
+            for (int i = 0; i < ww; ++i)
+                for (int c = 0; c < 3; ++c) acc += vb_sq((float)p[3 * i + c], fm[c]);
+        }
+        return sqrt((double)acc);
+    }
+    if (!h->on || !prev || prev->l + prev->r <= 0 || prev->u + prev->dn <= 0) {
+        memset(h, 0, sizeof *h);
+        vb_hist_add(h, R, x - w->l, x + w->r, y - w->u, y + w->dn);
+        h->on = 1;
+    } else {                   /* the ring the step added: full-width rows above / below, then the old rows' sides */
+        vb_hist_add(h, R, x - w->l, x + w->r, y - w->u, y - prev->u);
+        vb_hist_add(h, R, x - w->l, x + w->r, y + prev->dn, y + w->dn);
+        vb_hist_add(h, R, x - w->l, x - prev->l, y - prev->u, y + prev->dn);
+        vb_hist_add(h, R, x + prev->r, x + w->r, y - prev->u, y + prev->dn);
+    }
+    int64_t acc = 0;
+    for (int c = 0; c < 3; ++c) {
+        const float fm = (float)((double)h->sum[c] / n);
+        for (int v = 0; v < 256; ++v)
+            if (h->hist[c][v]) acc += h->hist[c][v] * vb_sq((float)v, fm);
+    }
+    return sqrt((double)acc);
+}
+
+/* The grown window of eligible pixel (x, y) and its block size (the last +4 counted, BlockSearch.cpp:129-145). */
+static int vb_grow(const wso_image *R, int bs0, double thres, int x, int y, vb_win *w, vb_hist *h)
+{
+    const int w2 = R->width, h2 = R->height;
+    int bs = bs0;
+    vb_win prev;
+    const vb_win *pp = NULL;
+    vb_clip(w2, h2, x, y, bs, w);
+    h->on = 0;
+    while (vb_texture(R, x, y, w, pp, h) < thres) {
+        vb_win g;
+        bs += 4;
+        vb_clip(w2, h2, x, y, bs, &g);
+        if (g.l == w->l && g.r == w->r && g.u == w->u && g.dn == w->dn) break;
+        prev = *w;
+        pp = &prev;
+        *w = g;
+    }
+    return bs;
+}
+
+static inline void vb_insert(vb_top *t, uint64_t c, int d, int k)
+{
+    /* d ascending: an equal cost ranks after every entry already held */
+    int i = t->n < k ? t->n : k;
+    if (i == k && !(c < t->c[k - 1])) return;
+    if (i == k) --i;
+    while (i > 0 && c < t->c[i - 1]) {
+        t->c[i] = t->c[i - 1];
+        t->d[i] = t->d[i - 1];
+        --i;
+    }
+    t->c[i] = c;
+    t->d[i] = d;
+    if (t->n < k) t->n++;
+}
+
+/* the direct 64-bit window cost at d (the raster pass's factored candidates outside the captured ones) */
+static uint64_t vb_cost_direct(const wso_image *L, const wso_image *R, int cost, int x, int y, const vb_win *w, int d)
+{
+    uint64_t acc = 0;
+    for (int yy = y - w->u; yy < y + w->dn; ++yy) {
+        const uint8_t *a = pix(L, yy, x + d - w->l), *b = pix(R, yy, x - w->l);
+        for (int i = 0; i < 3 * (w->l + w->r); ++i) {
+            int e = (int)a[i] - (int)b[i];
+            acc += cost == WSO_COST_SAD ? (uint64_t)(e < 0 ? -e : e) : (uint64_t)(e * e);
+        }
+    }
+    return acc;
+}
+
+static int var_block_right(const wso_image *L, const wso_image *R, int block_size, int min_d, int max_d,
+                           double smooth, double thres, int cost, int y0, int y1, double *out, int os, int threads,
+                           int *max_block_out)
+{
+    const int w1 = L->width, h1 = L->height, w2 = R->width, h2 = R->height;
+    const int height = h1 < h2 ? h1 : h2;
+    const int yb = height < y1 ? height : y1;
+    const int rows = yb > y0 ? yb - y0 : 0;
+    const size_t np = (size_t)rows * (size_t)w2;
+    const int K = smooth == 1.0 ? 1 : 3;
+    /* sqrt(c) / area strictly increasing over the sums that occur: c < 2^50 */
+    const double per = cost == WSO_COST_SAD ? 3.0 * 255.0 : 3.0 * 255.0 * 255.0;
+    if (per * (double)w2 * (double)h2 >= 1125899906842624.0) return WSF_ERR_UNSUPPORTED;
+
+    vb_win *win = malloc(sizeof(vb_win) * (np ? np : 1));
+    unsigned char *elig = malloc(np ? np : 1);
+    vb_top *top = malloc(sizeof(vb_top) * (np ? np : 1));
+    uint64_t *cap = malloc(sizeof(uint64_t) * 3 * (np ? np : 1));   /* costs at d = 0, x - 1, x */
+    if (!win || !elig || !top || !cap) {
+        free(win), free(elig), free(top), free(cap);
+        return WSO_ERR_ARG;
+    }
+    int max_block = block_size, geometry_error = 0, err = 0;
+
+    /* 1. windows */
+#pragma omp parallel num_threads(threads) if (threads > 1) reduction(max : max_block) reduction(| : geometry_error, err)
+    {
+        vb_hist *h = malloc(sizeof(vb_hist));
+        err |= !h;
+#pragma omp for schedule(dynamic, 1)
+        for (int y = y0; y < yb; ++y) {
+            for (int x = 0; x < w2; ++x) {
+                const size_t i = (size_t)(y - y0) * w2 + x;
+                top[i].n = 0;
+                cap[3 * i] = cap[3 * i + 1] = cap[3 * i + 2] = UINT64_MAX;
+                elig[i] = !black(R, y, x);
+                if (!elig[i]) continue;
+                if (!h) continue;
+                const int bs = vb_grow(R, block_size, thres, x, y, &win[i], h);
+                if (bs > max_block) max_block = bs;
+                /* the first candidate's window must lie in the left image (BlockSearch.cpp:147-154) */
+                const long cx = (long)x + min_d;
+                if (max_d > min_d && cx + win[i].r < w1 && (cx - win[i].l < 0 || y + win[i].dn > h1))
+                    geometry_error = 1;
+            }
+        }
+        free(h);
+    }
+    if (geometry_error || err) {
+        free(win), free(elig), free(top), free(cap);
+        return err ? WSO_ERR_ARG : WSO_ERR_GEOMETRY;
+    }
+
+    /* 2. costs: d over every candidate any pixel can have (cx - left >= 0 gives d >= 1 - w2, cx + right < w1 d < w1) */
+    const int dlo = min_d > 1 - w2 ? min_d : 1 - w2;
+    const int dhi = max_d - 1 < w1 - 1 ? max_d - 1 : w1 - 1;
+    /* the table covers rows [0, height): every candidate's window has y + down <= h1 (checked above) and < h2 */
+    const int sh = height, sw = w2 + 1;
+    uint64_t *S = dhi >= dlo && rows ? malloc(sizeof(uint64_t) * (size_t)(sh + 1) * (size_t)sw) : NULL;
+    err = dhi >= dlo && rows && !S;
+    if (S) {
+#pragma omp parallel num_threads(threads) if (threads > 1)
+        for (int d = dlo; d <= dhi; ++d) {
+#pragma omp for schedule(static)
+            for (int y = 0; y <= sh; ++y) {
+                uint64_t *s = S + (size_t)y * sw;
+                s[0] = 0;
+                if (y == 0) {
+                    memset(s, 0, sizeof(uint64_t) * (size_t)sw);
+                    continue;
+                }
+                const uint8_t *b = pix(R, y - 1, 0), *a = L->data + (size_t)(y - 1) * L->stride;
+                uint64_t run = 0;
+                for (int x = 0; x < w2; ++x) {
+                    const int xl = x + d;
+                    if (xl >= 0 && xl < w1) {
+                        const uint8_t *p = a + 3 * (size_t)xl, *q = b + 3 * (size_t)x;
+                        const int e0 = (int)p[0] - (int)q[0], e1 = (int)p[1] - (int)q[1], e2 = (int)p[2] - (int)q[2];
+                        run += cost == WSO_COST_SAD ? (uint64_t)(abs(e0) + abs(e1) + abs(e2))
+                                                    : (uint64_t)(e0 * e0 + e1 * e1 + e2 * e2);
+                    }
+                    s[x + 1] = run;
+                }
+            }
+#pragma omp for schedule(static)
+            for (int xa = 0; xa < sw; xa += 256) {
+                const int xe = xa + 256 < sw ? xa + 256 : sw;
+                for (int y = 2; y <= sh; ++y) {
+                    uint64_t *s = S + (size_t)y * sw, *t = s - sw;
+                    for (int x = xa; x < xe; ++x) s[x] += t[x];
+                }
+            }
+#pragma omp for schedule(dynamic, 4)
+            for (int y = y0; y < yb; ++y) {
+                for (int x = 0; x < w2; ++x) {
+                    const size_t i = (size_t)(y - y0) * w2 + x;
+                    if (!elig[i]) continue;
+                    const vb_win *w = &win[i];
+                    if (w->l + w->r == 0 || w->u + w->dn == 0) continue;
+                    if (d < min_d || x + d + w->r >= w1) continue;   /* not a candidate of this pixel */
+                    const uint64_t *ra = S + (size_t)(y - w->u) * sw, *rb = S + (size_t)(y + w->dn) * sw;
+                    const int ca = x - w->l, cb = x + w->r;
+                    const uint64_t c = rb[cb] - rb[ca] - ra[cb] + ra[ca];
+                    vb_insert(&top[i], c, d, K);
+                    if (d == 0) cap[3 * i] = c;
+                    if (d == x - 1) cap[3 * i + 1] = c;
+                    if (d == x) cap[3 * i + 2] = c;
+                }
+            }
+        }
+    }
+    free(S);
+
+    /* 3. decisions */
+    if (!err) {
+        for (int y = y0; y < yb; ++y) {
+            double *orow = out + (size_t)y * os;
+            const double *up = y >= 1 ? out + (size_t)(y - 1) * os : NULL;
+            for (int x = 0; x < w2; ++x) {
+                const size_t i = (size_t)(y - y0) * w2 + x;
+                if (!elig[i]) continue;
+                const vb_top *t = &top[i];
+                if (t->n == 0) {                              /* no candidate (or a zero-area window: 0/0) */
+                    orow[x] = (double)(0 - x);
+                    continue;
+                }
+                if (smooth == 1.0) {
+                    orow[x] = (double)t->d[0];
+                    continue;
+                }
+                const vb_win *w = &win[i];
+                const int area = (w->l + w->r) * (w->u + w->dn);
+                const int hi = max_d - 1 < w1 - 1 - w->r - x ? max_d - 1 : w1 - 1 - w->r - x;
+                /* the d the factor reaches: -d == the stored value above / to the left (BlockSearch.cpp:160-165) */
+                int fd[2], fk[2], nf = 0;
+                const double nb[2] = {up ? up[x] : NAN, x >= 1 ? orow[x - 1] : NAN};
+                for (int k = 0; k < 2; ++k) {
+                    const double v = -nb[k];
+                    if (!(v >= (double)min_d && v <= (double)hi)) continue;
+                    const int d = (int)v;
+                    if (nf == 1 && fd[0] == d) {
+                        fk[0]++;
+                        continue;
+                    }
+                    fd[nf] = d;
+                    fk[nf++] = 1;
+                }
+                double best = DBL_MAX;
+                int best_d = 0, found = 0;
+                for (int j = 0; j < t->n; ++j) {             /* the best candidate the factor does not reach */
+                    const int d = t->d[j];
+                    if ((nf > 0 && fd[0] == d) || (nf > 1 && fd[1] == d)) continue;
+                    best = (cost == WSO_COST_SAD ? (double)t->c[j] : sqrt((double)t->c[j])) / (double)area;
+                    best_d = d;
+                    found = 1;          /* (a window's dist is finite: below DBL_MAX) */
+                    break;
+                }
+                for (int k = 0; k < nf; ++k) {
+                    const int d = fd[k];
+                    uint64_t c = d == 0 ? cap[3 * i] : d == x - 1 ? cap[3 * i + 1] : d == x ? cap[3 * i + 2] : UINT64_MAX;
+                    if (c == UINT64_MAX) c = vb_cost_direct(L, R, cost, x, y, w, d);
+                    double v = (cost == WSO_COST_SAD ? (double)c : sqrt((double)c)) / (double)area;
+                    for (int m = 0; m < fk[k]; ++m) v *= smooth;
+                    if (v < best || (v == best && found && d < best_d)) {
+                        best = v;
+                        best_d = d;
+                        found = 1;
+                    }
+                }
+                orow[x] = found ? (double)best_d : (double)(0 - x);
+            }
+        }
+    }
+    free(win), free(elig), free(top), free(cap);
+    if (err) return WSO_ERR_ARG;
+    if (max_block_out) *max_block_out = max_block;
+    return WSO_OK;
+}
+
+int wsf_block_right_vb(const wso_image *L, const wso_image *R, int block_size,
+                       int min_disparity, int max_disparity, double smooth,
+                       int var_block, double thres, int cost, int subpixel, int y0, int y1,
+                       double *out, int out_stride, int *max_block_out, int threads)
 {
     if (!image_ok(L) || !image_ok(R) || !out || block_size < 1 ||
         out_stride < R->width || (cost != WSO_COST_SSD && cost != WSO_COST_SAD))
         return WSO_ERR_ARG;
-    if (var_block) return WSF_ERR_UNSUPPORTED;
     geom g;
     memset(&g, 0, sizeof g);
     g.right = 1;
@@ -550,9 +882,14 @@ int wsf_block_right(const wso_image *L, const wso_image *R, int block_size,
     const int height = g.h1 < g.h2 ? g.h1 : g.h2;
     if (y0 < 0 || y1 > g.h2 || y0 > y1) return WSO_ERR_ARG;
     if (smooth != 1.0 && (y0 != 0 || subpixel)) return WSO_ERR_RANGE;
-    if (!sums_fit(2 * g.half, 2 * g.half, cost)) return WSF_ERR_UNSUPPORTED;
+    if (var_block && subpixel) return WSF_ERR_UNSUPPORTED;
+    if (!var_block && !sums_fit(2 * g.half, 2 * g.half, cost)) return WSF_ERR_UNSUPPORTED;
 
     for (int y = 0; y < g.h2; ++y) memset(out + (size_t)y * out_stride, 0, sizeof(double) * (size_t)g.w2);
+    threads = threads_of(threads);
+    if (var_block)
+        return var_block_right(L, R, block_size, min_disparity, max_disparity, smooth, thres, cost, y0, y1, out,
+                               out_stride, threads, max_block_out);
     const int yb = height < y1 ? height : y1;
     if (right_geometry_error(&g, y0, yb)) return WSO_ERR_GEOMETRY;
 
@@ -563,7 +900,21 @@ int wsf_block_right(const wso_image *L, const wso_image *R, int block_size,
     g.d0 = dlo;
     g.nd = dhi >= dlo ? dhi - dlo + 1 : 0;
     g.ostride = g.wb + g.nd;
-    threads = threads_of(threads);
-    return smooth == 1.0 ? search_plain(&g, subpixel, y0, yb, out, out_stride, threads)
-                         : search_smooth(&g, smooth, y0, yb, out, out_stride, threads);
+    int rc = smooth == 1.0 ? search_plain(&g, subpixel, y0, yb, out, out_stride, threads)
+                           : search_smooth(&g, smooth, y0, yb, out, out_stride, threads);
+    if (rc == WSO_OK && max_block_out) *max_block_out = block_size;
+    return rc;
+}
+
+int wsf_block_right(const wso_image *L, const wso_image *R, int block_size,
+                    int min_disparity, int max_disparity, double smooth,
+                    int var_block, int cost, int subpixel, int y0, int y1,
+                    double *out, int out_stride, int threads)
+{
+    if (!image_ok(L) || !image_ok(R) || !out || block_size < 1 ||
+        out_stride < R->width || (cost != WSO_COST_SSD && cost != WSO_COST_SAD))
+        return WSO_ERR_ARG;
+    if (var_block) return WSF_ERR_UNSUPPORTED;   /* (no thres here: wsf_block_right_vb) */
+    return wsf_block_right_vb(L, R, block_size, min_disparity, max_disparity, smooth, 0, 0.0, cost, subpixel, y0, y1,
+                              out, out_stride, NULL, threads);
 }

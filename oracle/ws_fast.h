@@ -10,8 +10,9 @@
  * that the two restatements pin each other (tests/test_fast_reference.py).
  *
  * Images and outputs as in ws_oracle.h.  Return codes are the WSO_* codes, plus
- * WSF_ERR_UNSUPPORTED for what this reference does not implement (var_block,
- * block sizes whose window sums would not fit 32 bits).
+ * WSF_ERR_UNSUPPORTED for what this reference does not implement (var_block
+ * together with sub-pixel refinement, block sizes whose window sums would not
+ * fit 32 bits without var_block).
  */
 #ifndef WS_FAST_H
 #define WS_FAST_H
@@ -35,6 +36,14 @@ int wsf_block_right(const wso_image *L, const wso_image *R, int block_size,
                     int min_disparity, int max_disparity, double smooth,
                     int var_block, int cost, int subpixel, int y0, int y1,
                     double *out, int out_stride, int threads);
+
+/* wso_block_right's semantics, var_block, thres and max_block_out (may be NULL) included.  var_block
+ * runs a route of its own (ws_fast.c): every pixel's window from a value histogram, its costs from
+ * one 64-bit summed-area table per disparity, O(H * W * D) whatever the windows grow to. */
+int wsf_block_right_vb(const wso_image *L, const wso_image *R, int block_size,
+                       int min_disparity, int max_disparity, double smooth,
+                       int var_block, double thres, int cost, int subpixel, int y0, int y1,
+                       double *out, int out_stride, int *max_block_out, int threads);
 
 #ifdef __cplusplus
 }

@@ -54,11 +54,11 @@ static uint64_t window_sum(const wso_image *A, int ax, int ay,
     for (int r = 0; r < wh; ++r) {
         const uint8_t *a = px(A, ay + r, ax);
         const uint8_t *b = px(B, by + r, bx);
-        uint32_t row = 0;
+        uint64_t row = 0; /* (a grown varBlock window's row can pass 2^32: 3 * 255^2 * ww for ww > 22017) */
         for (int i = 0; i < 3 * ww; ++i) {
             int d = (int)a[i] - (int)b[i];
             if (d < 0) d = -d;
-            row += (cost == WSO_COST_SAD) ? (uint32_t)d : (uint32_t)(d * d);
+            row += (cost == WSO_COST_SAD) ? (uint64_t)d : (uint64_t)(d * d);
         }
         acc += row;
     }

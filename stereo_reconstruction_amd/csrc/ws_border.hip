@@ -573,7 +573,7 @@ hipError_t launch_refine(const GenericArgs &g, hipStream_t s)
 // ------------------------------------------------------------------------------------------
 
 __global__ void __launch_bounds__(256) ws_varblock_kernel(const GenericArgs g, double thres,
-                                                          int16_t *__restrict__ bs_plane, int bs_pitch,
+                                                          int32_t *__restrict__ bs_plane, int bs_pitch,
                                                           int *__restrict__ max_block)
 {
     const int lane = threadIdx.x & 63;
@@ -622,7 +622,7 @@ __global__ void __launch_bounds__(256) ws_varblock_kernel(const GenericArgs g, d
         // A window that did not grow is the ordinary right-view window: the marching / ring kernels
         // have searched it already (launch order in ws_capi.cpp), only the block size is recorded.
         if (bs == g.block_size) {
-            if (lane == 0) bs_plane[(size_t)y * bs_pitch + x] = (int16_t)bs;
+            if (lane == 0) bs_plane[(size_t)y * bs_pitch + x] = bs;
             return;
         }
         // the search with this pixel's window: lanes over d, d ascending inside a lane
@@ -648,11 +648,11 @@ __global__ void __launch_bounds__(256) ws_varblock_kernel(const GenericArgs g, d
     }
     if (lane == 0) {
         g.out[(size_t)y * g.out_pitch + x] = val;
-        bs_plane[(size_t)y * bs_pitch + x] = (int16_t)min(bs, 32767);
+        bs_plane[(size_t)y * bs_pitch + x] = bs; // (a grown window's bs passes 32767 past ~16.4k pixels of width / height)
     }
 }
 
-hipError_t launch_varblock(const GenericArgs &g, double thres, int16_t *bs_plane, int bs_pitch, int *max_block,
+hipError_t launch_varblock(const GenericArgs &g, double thres, int32_t *bs_plane, int bs_pitch, int *max_block,
                            hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(max_block, 0, sizeof(int), s);

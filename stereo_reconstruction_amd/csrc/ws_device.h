@@ -140,9 +140,18 @@ __device__ __forceinline__ unsigned long long window_cost64(const uint8_t *a, in
                                                             int ww, int wh, int ssd)
 {
     unsigned long long acc = 0; // grown (varBlock) windows can exceed 32 bits
+    // ... and so can one row of one: 3 * 255^2 * ww >= 2^32 from ww = 22017 on (SSD)
+    const bool wide = 3ll * (ssd ? 255 * 255 : 255) * ww >= (1ll << 32);
     for (int r = 0; r < wh; ++r) {
         const uint8_t *pa = a + (size_t)r * sa;
         const uint8_t *pb = b + (size_t)r * sb;
+        if (wide) {
+            for (int i = 0; i < 3 * ww; ++i) {
+                const int d = (int)pa[i] - (int)pb[i];
+                acc += ssd ? (unsigned long long)(d * d) : (unsigned long long)(d < 0 ? -d : d);
+            }
+            continue;
+        }
         uint32_t row = 0;
         for (int i = 0; i < 3 * ww; ++i) {
             const int d = (int)pa[i] - (int)pb[i];

@@ -89,7 +89,7 @@ struct GenericArgs {
     int16_t *out16; // if set, the search kernels store the map as 16-bit integers here (same pitch, in elements) instead of floats to `out`:
                     // the caller (ws_capi.cpp) knows every value is an integer in [-32767, 32767]
     // varBlock (right view): per-pixel block size chosen by ws_varblock_kernel, or null
-    const int16_t *bs_plane;
+    const int32_t *bs_plane;
     int bs_pitch;
 };
 hipError_t launch_generic(const GenericArgs &g, hipStream_t s);
@@ -146,8 +146,8 @@ hipError_t launch_mesh_count(const float *pos, const uint8_t *col, int w, int h,
 hipError_t launch_mesh_write(const float *pos, const uint8_t *col, int w, int h, float thr, const unsigned long long *block_off,
                              const unsigned long long *meta, char *text, hipStream_t s);
 // varBlock (BlockSearch.cpp:125-145, right view): per-pixel window growth + search, one wave per pixel.
-// bs_plane: w2 x h2 int16 (pitch bs_pitch), max_block: one device int (max grown block size)
-hipError_t launch_varblock(const GenericArgs &g, double thres, int16_t *bs_plane, int bs_pitch, int *max_block,
+// bs_plane: w2 x h2 int32 (pitch bs_pitch), max_block: one device int (max grown block size)
+hipError_t launch_varblock(const GenericArgs &g, double thres, int32_t *bs_plane, int bs_pitch, int *max_block,
                            hipStream_t s);
 // Left-right consistency check (ws_lr.hip; the rules are in include/ws_stereo.h).  Map 0 is the left map (partner column
 // x - rint(v)), map 1 the right map (x + rint(v)); in/out pitches in elements.

@@ -17,7 +17,7 @@ struct SearchResult {
     Canon canon{};
     Plane pa{}, pb{};
     int32_t *cost = nullptr;           // the winners' costs (pitch canon.wa), or null
-    const int16_t *bs_plane = nullptr; // varBlock: the windows ws_varblock_kernel chose (pitch (R->width + 63) & ~63)
+    const int32_t *bs_plane = nullptr; // varBlock: the windows ws_varblock_kernel chose (pitch (R->width + 63) & ~63)
 };
 
 // the brute-force kernels' view of a search (ws_kernels.h)
@@ -65,11 +65,11 @@ int run_canonical(Searcher &S, std::string *err, const ws_params *p, const ws_im
         int rc = run_canonical(S, err, &q, L, R, out, out_stride, out16, keep_cost, pack_planes, s, res);
         if (rc != WS_OK) return rc;
         const int bs_pitch = (R->width + 63) & ~63;
-        if ((rc = ensure(err, S.bs_plane, (size_t)bs_pitch * R->height * 2)) != WS_OK) return rc;
+        if ((rc = ensure(err, S.bs_plane, (size_t)bs_pitch * R->height * sizeof(int32_t))) != WS_OK) return rc;
         if ((rc = ensure(err, S.max_block, 64)) != WS_OK) return rc;
-        WS_HIP(err, launch_varblock(ga, p->thres, static_cast<int16_t *>(S.bs_plane.p), bs_pitch,
+        WS_HIP(err, launch_varblock(ga, p->thres, static_cast<int32_t *>(S.bs_plane.p), bs_pitch,
                                     static_cast<int *>(S.max_block.p), s));
-        res->bs_plane = static_cast<const int16_t *>(S.bs_plane.p);
+        res->bs_plane = static_cast<const int32_t *>(S.bs_plane.p);
         S.launched("ws_varblock_kernel", 256, (int)(((long long)R->width * R->height + 3) / 4), 0);
         S.var_block_ran = true;
         return WS_OK;

@@ -193,10 +193,166 @@ def test_medium_shape_against_the_oracle(oracle):
                               oracle.block_right(left, right, bs, 0, 128, cost=cost, threads=8))
 
 
-def test_var_block_is_refused_not_approximated(oracle):
+# ---- varBlock (BlockSearch.cpp:125-145): fast_right's own route (value histograms, per-d summed-area tables) -------
+VB_THRES = [-1.0, 0.0, 5.0, 19.0, 60.0, 1e4, np.inf]
+VB_SMOOTHS = [1.0, 0.9, 0.0, -0.5, np.inf]
+
+
+def _patched(rng, img):
+    """Flat and few-level patches (the texture test fails there and windows grow), sometimes on a border."""
+    h, w = img.shape[:2]
+    for _ in range(int(rng.integers(1, 4))):
+        ph, pw = int(rng.integers(1, h + 1)), int(rng.integers(1, w + 1))
+        y, x = int(rng.integers(0, h - ph + 1)), int(rng.integers(0, w - pw + 1))
+        if rng.random() < 0.5:
+            img[y:y + ph, x:x + pw] = rng.integers(1, 256, 3, dtype=np.uint8)
+        else:
+            img[y:y + ph, x:x + pw] = (rng.integers(0, 2, size=(ph, pw, 3)) * int(rng.integers(1, 12)) + 90).astype(np.uint8)
+    return img
+
+
+def _var_block_case(rng):
+    w1, h1 = int(rng.integers(1, 40)), int(rng.integers(1, 18))
+    w2 = max(1, w1 + int(rng.integers(-8, 9))) if rng.random() < 0.4 else w1
+    h2 = max(1, h1 - int(rng.integers(0, 4))) if rng.random() < 0.4 else h1           # h1 >= h2
+    mind = int(rng.integers(1, 6)) if rng.random() < 0.4 else 0
+    maxd = int(rng.integers(mind, mind + 30))
+    kind = rng.choice(["textured", "random", "levels2", "levels3", "flat"])
+    if kind == "textured":
+        left, right, _ = make_pair(w1, h1, max(2, maxd), int(rng.integers(1 << 30)), right_width=w2, right_height=h2)
+    elif kind == "flat":
+        left = np.full((h1, w1, 3), int(rng.integers(1, 256)), np.uint8)
+        right = np.full((h2, w2, 3), int(rng.integers(1, 256)), np.uint8)
+    else:
+        left, right = _image(rng, h1, w1, kind), _image(rng, h2, w2, kind)
+    left, right = _patched(rng, left), _patched(rng, right)
+    if rng.random() < 0.3:                      # black pixels: skipped, and a window beside them has texture
+        right[int(rng.integers(h2)), int(rng.integers(w2)):][:3] = 0
+    return dict(left=left, right=right, bs=int(rng.integers(1, 12)), mind=mind, maxd=maxd,
+                thres=float(VB_THRES[int(rng.integers(len(VB_THRES)))]),
+                smooth=float(VB_SMOOTHS[int(rng.integers(len(VB_SMOOTHS)))]),
+                cost="ssd" if rng.random() < 0.5 else "sad")
+
+
+def _var_block_compare(oracle, c, with_brute=False):
+    args = (c["left"], c["right"], c["bs"], c["mind"], c["maxd"])
+    kw = dict(smooth=c["smooth"], var_block=True, thres=c["thres"], cost=c["cost"], return_max_block=True)
+    want, want_err = _run(oracle.block_right, *args, threads=4, **kw)
+    got, got_err = _run(oracle.fast_right, *args, threads=3, **kw)
+    desc = {k: v for k, v in c.items() if k not in ("left", "right")}
+    desc.update(shapes=(c["left"].shape, c["right"].shape))
+    assert got_err is want_err, desc
+    if want_err is not None:
+        return "error"
+    assert want[1] == got[1], (desc, want[1], got[1])
+    assert np.array_equal(got[0], want[0]), (desc, np.argwhere(got[0] != want[0])[:5])
+    if with_brute:
+        ref = brute.block_right_py(*args, smooth=c["smooth"], cost=c["cost"], var_block=True, thres=c["thres"])
+        assert np.array_equal(got[0], ref[0]) and got[1] == ref[1], ("brute", desc)
+    return "grown" if want[1] > c["bs"] else "ok"
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_var_block_equals_the_oracle_on_random_cases(oracle, seed):
+    """Tiny images with flat and quantised patches, every thres class, both costs, min_disparity > 0, unequal sizes with
+    h1 >= h2, smoothFactor 1 / 0.9 / 0 / -0.5 / inf; the NumPy brute force on the smallest ones."""
+    rng = np.random.default_rng(4400 + seed)
+    outcomes = []
+    for _ in range(25):
+        c = _var_block_case(rng)
+        small = c["left"].shape[0] * c["left"].shape[1] <= 240
+        outcomes.append(_var_block_compare(oracle, c, with_brute=small))
+    assert outcomes.count("grown") >= 5, outcomes        # windows really grew in most seeds' cases
+
+
+def test_var_block_medium_shapes_threads_and_row_bands(oracle):
+    """Windows past 63 on a 240 x 90 pair with flat patches wider than 64 px, D past 64 (several disparities per device
+    lane), both costs; row bands and thread counts do not change the map."""
+    left, right, gt = make_pair(240, 90, 96, 17)
+    left[10:70, 40:160] = 120
+    right[10:70, 0:120] = 120
+    right[80:, 200:] = 0
+    for cost in ("ssd", "sad"):
+        for smooth in (1.0, 0.9):
+            want = oracle.block_right(left, right, 5, 2, 96, smooth=smooth, var_block=True, cost=cost, threads=8,
+                                      return_max_block=True)
+            assert want[1] > 63
+            for threads in (1, 5):
+                got = oracle.fast_right(left, right, 5, 2, 96, smooth=smooth, var_block=True, cost=cost, threads=threads,
+                                        return_max_block=True)
+                assert got[1] == want[1] and np.array_equal(got[0], want[0]), (cost, smooth, threads)
+    band = oracle.fast_right(left, right, 5, 2, 96, var_block=True, rows=(30, 61), threads=3, return_max_block=True)
+    want = oracle.block_right(left, right, 5, 2, 96, var_block=True, rows=(30, 61), return_max_block=True)
+    assert band[1] == want[1] and np.array_equal(band[0], want[0])
+    with pytest.raises(NotImplementedError):            # (sub-pixel together with varBlock: no fast route)
+        oracle.fast_right(left, right, 5, 0, 8, var_block=True, subpixel=True)
+    assert oracle.fast_right(left, right, 5, 0, 8, return_max_block=True)[1] == 5
+
+
+def test_var_block_with_subpixel_is_refused_not_approximated(oracle):
+    """What the fast reference does not implement raises: varBlock together with sub-pixel refinement, and varBlock
+    through wsf_block_right, the entry without thres (wsf_block_right_vb takes it)."""
+    import ctypes
     left, right, _ = make_pair(40, 20, 8, 1)
     with pytest.raises(NotImplementedError):
-        oracle.fast_right(left, right, 5, 0, 8, var_block=True)
+        oracle.fast_right(left, right, 5, 0, 8, var_block=True, subpixel=True)
+    La, Li = oracle._img(left)
+    Ra, Ri = oracle._img(right)
+    out = np.zeros(right.shape[:2], dtype=np.float64)
+    rc = oracle.lib().wsf_block_right(ctypes.byref(Li), ctypes.byref(Ri), 5, 0, 8, 1.0, 1, 0, 0, 0, right.shape[0],
+                                      out.ctypes.data, out.shape[1], 1)
+    assert rc == -4
+    assert oracle.lib().wsf_block_right(ctypes.byref(Li), ctypes.byref(Ri), 5, 0, 8, 1.0, 0, 0, 0, 0, right.shape[0],
+                                        out.ctypes.data, out.shape[1], 1) == 0
+    assert np.array_equal(out, oracle.block_right(left, right, 5, 0, 8))
+
+
+def _scenario_a():
+    right = np.zeros((3, 22200, 3), np.uint8)
+    right[1, 22100] = 1
+    right[:, 50] = 255
+    left = np.full((3, 22210, 3), 255, np.uint8)
+    left[:, 50] = 0
+    left[:, 1000:1131] = 0
+    return left, right
+
+
+def test_var_block_row_sums_past_32_bits(oracle):
+    """Pixel (1, 22100) grows to block 44101 (a 44100 x 2 window): one row of its SSD window passes 2^32 at d = 1..3
+    (8 589 931 023) and at d = 0 (8 590 321 173), so d = 1 wins.  Summed in 32 bits per row, d = 0 (386 581) would."""
+    left, right = _scenario_a()
+    kw = dict(var_block=True, thres=10.0, return_max_block=True)
+    slow = oracle.block_right(left, right, 5, 0, 4, **kw)
+    fast = oracle.fast_right(left, right, 5, 0, 4, **kw)
+    ref_map, ref_mb = brute.block_right_py(left, right, 5, 0, 4, var_block=True, thres=10.0, only=(1, 22100))
+    assert slow[1] == fast[1] == ref_mb == 44101
+    assert slow[0][1, 22100] == fast[0][1, 22100] == ref_map[1, 22100] == 1
+    assert np.array_equal(slow[0], fast[0])
+
+
+@pytest.mark.parametrize("scene", ["wide", "tall"])
+def test_var_block_block_sizes_past_16_bits(oracle, scene):
+    """A window that grows to block 32781 (half-width 16390), smoothFactor 0.9: value 1 at the grown pixel."""
+    if scene == "wide":
+        right = np.zeros((3, 16500, 3), np.uint8)
+        right[1, 16450] = 100
+        right[:, 60] = 255
+        left = np.zeros((3, 16520, 3), np.uint8)
+        left[:, 61] = 255
+        yx = (1, 16450)
+    else:
+        right = np.zeros((16500, 3, 3), np.uint8)
+        right[16450, 1] = 100
+        right[60, :] = 255
+        left = np.zeros((16500, 12, 3), np.uint8)
+        left[60, 1:3] = 255
+        yx = (16450, 1)
+    kw = dict(smooth=0.9, var_block=True, thres=200.0, return_max_block=True)
+    slow = oracle.block_right(left, right, 5, 0, 8, **kw)
+    fast = oracle.fast_right(left, right, 5, 0, 8, **kw)
+    assert slow[1] == fast[1] == 32781
+    assert slow[0][yx] == fast[0][yx] == 1
+    assert np.array_equal(slow[0], fast[0])
 
 
 def _tall_tie_pair(rng, w, h, period):

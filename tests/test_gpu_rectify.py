@@ -144,8 +144,9 @@ def test_rectify_device_4k(gpu_ctx):
 
 # ---- ws_search_unrectified_host --------------------------------------------------------------------------------------
 
-def _chain(oracle, left, right, H, Hp, view, bs, mind, maxd, smooth, cost):
-    """rectify (restatement) -> fast exact search -> warp back with inv(H_) (rectification.cpp:66-88, :486-493)."""
+def _chain(oracle, left, right, H, Hp, view, bs, mind, maxd, smooth, cost, **kw):
+    """rectify (restatement) -> fast exact search -> warp back with inv(H_) (rectification.cpp:66-88, :486-493).
+    kw: the right view's var_block / thres."""
     lw, lh = rr.rectified_size(H, left.shape[1], left.shape[0])
     rw, rh = rr.rectified_size(Hp, right.shape[1], right.shape[0])
     rl = rr.warp_linear_u8(left, H, (lh, lw))
@@ -154,7 +155,7 @@ def _chain(oracle, left, right, H, Hp, view, bs, mind, maxd, smooth, cost):
         m = oracle.fast_left(rl, rrt, bs, mind, maxd, smooth=smooth, cost=cost)
         shape = left.shape[:2]
     else:
-        m = oracle.fast_right(rl, rrt, bs, mind, maxd, smooth=smooth, cost=cost)
+        m = oracle.fast_right(rl, rrt, bs, mind, maxd, smooth=smooth, cost=cost, **kw)
         shape = right.shape[:2]
     return oracle.warp_nearest(m, rr.inv3(H), shape), rl, rrt
 
@@ -217,9 +218,22 @@ def test_unrectified_search_config2_sized(wslib, gpu_ctx, oracle):
     assert np.array_equal(got, want), np.argwhere(got != want)[:5]
 
 
+def test_unrectified_search_var_block_against_the_cpu_chain(wslib, gpu_ctx, oracle):
+    """varBlock: the unrectified call against the CPU chain (rectify restatement -> fast exact varBlock search -> warp
+    back); the warped black corners of the rectified right image and the windows that grow beside them included."""
+    left, right, _ = make_pair(260, 160, 32, seed=12)
+    H, Hp = _pair_homographies(260, 160, 260, 160)
+    for smooth, thres in ((0.9, 10.0), (0.9, 120.0), (1.0, 150.0)):
+        want, rl, rrt = _chain(oracle, left, right, H, Hp, "right", 7, 0, 40, smooth, "ssd", var_block=True, thres=thres)
+        got, gl, gr = _unrect(wslib, gpu_ctx, left, right, H, Hp, "right", 7, 0, 40, smooth, "ssd", var_block=True,
+                              thres=thres)
+        assert np.array_equal(gl, rl) and np.array_equal(gr, rrt)
+        assert np.array_equal(got, want), (smooth, thres, np.argwhere(got != want)[:5])
+
+
 def test_unrectified_search_var_block_and_subpixel_take_the_device_path(wslib, gpu_ctx, oracle):
-    """varBlock and sub-pixel have no fast reference: the call must equal ws_search_host on the rectified images, warped
-    back (the same device path, the same warp)."""
+    """The call must equal ws_search_host on the rectified images, warped back (the same device path, the same warp);
+    sub-pixel has no fast reference, varBlock is also compared with the CPU chain above."""
     left, right, _ = make_pair(260, 160, 32, seed=12)
     H, Hp = _pair_homographies(260, 160, 260, 160)
     lw, lh = rr.rectified_size(H, 260, 160)
