@@ -281,6 +281,57 @@ int ws_filter_speckles_host(ws_context *ctx, float *map, int w, int h, int strid
 /* {pixels set to new_val, regions removed} by the last filter of this context; waits for that filter's stream. */
 int ws_last_speckle_counts(ws_context *ctx, unsigned long long counts[2]);
 
+/* ---- semi-global matching (extension) ---------------------------------------------------- */
+/*
+ * Hirschmueller's cost aggregation along image paths over the block search's exact window costs.  p: view LEFT or
+ * RIGHT, cost, block_size, the disparity range and subpixel, as for ws_search_*; smooth_factor must be 1.  For each pixel
+ * p of the output map the block search (smoothFactor 1, no varBlock) defines
+ *   * K(p): its candidate disparities, a contiguous interval or empty;
+ *   * C(p, d) for d in K(p): the exact integer window cost (SSD: the sum of squares before the square root; right view:
+ *     the clipped window's sum before the area division).
+ *   1. Node: p lies inside the searched region (left view: rows [half, min(h1,h2) - half), columns [half, w1 - half);
+ *      right view: rows < min(h1,h2)), is not black (the view's own black test) and K(p) is not empty.
+ *   2. Path cost, for each direction r with predecessor q = p - r.  If q is outside the image or not a node,
+ *      Lr(p,d) = C(p,d): paths restart after black pixels, outside the region and at pixels without candidates.  Else,
+ *      with m(q) = min over k in K(q) of Lr(q,k):
+ *        Lr(p,d) = C(p,d) + min(Lr(q,d), Lr(q,d-1) + P1, Lr(q,d+1) + P1, m(q) + P2) - m(q),
+ *      leaving out a term whose disparity is not in K(q); the last term is always there.
+ *      paths 4: r = (1,0) (-1,0) (0,1) (0,-1), i.e. predecessors (x-1,y) (x+1,y) (x,y-1) (x,y+1); 8: also the diagonals.
+ *   3. S(p,d) = the sum of Lr(p,d) over the paths.  A node's value is the argmin of S over K(p), ties as the view breaks
+ *      them: left view the largest d, right view the smallest d.
+ *   4. Non-nodes get what the block search stores: not black, no candidate: x (left view) or -x (right view); black or
+ *      outside the region: 0.
+ *   5. subpixel = 1: num = S(d-1) - S(d+1), den = S(d-1) - 2 S(d) + S(d+1), exact; refined only if d-1 and d+1 are in
+ *      K(p) and den > 0, to (float)d + (float)(num / (2.0 * den)).
+ *   6. The arithmetic is exact (C < 2^30 for block_size <= 63, Lr <= C + P2 < 2^32, S < 2^35): the storage widths are
+ *      picked from a bound on the host, and the map equals the exact one.
+ * Identity: with P1 = P2 = 0, S = paths * C for any paths, and the map equals ws_search_* with smoothFactor 1 bit for bit,
+ * the sub-pixel map included.
+ * Refusals: every refusal of ws_validate; WS_ERR_UNSUPPORTED for WS_VIEW_LINEAR, smooth_factor != 1, var_block in the
+ * right view, more than 2048 disparities left after the geometry's clip (left view min(maxD, w1 - 1 - 2 half), right view
+ * min(maxD, w1) - minD), a map of 2^31 pixels or more; WS_ERR_ARG for a null sgm, paths not 4 or 8, p1 < 0, p2 < p1.
+ * The scratch (ws_sgm_scratch_bytes) belongs to the context and grows on demand; a failed allocation is WS_ERR_NOMEM and
+ * leaves the context usable.  A map feeds ws_lr_check_device, ws_filter_speckles_device and the consumers as it is.
+ */
+typedef struct {
+    int paths; /* 4: predecessors (x-1,y) (x+1,y) (x,y-1) (x,y+1); 8: also the four diagonal ones */
+    int p1;    /* penalty for a disparity change of 1 between path neighbours, in cost units, >= 0 */
+    int p2;    /* penalty for a larger change, >= p1 */
+} ws_sgm_params;
+
+/* The argument checks of the SGM calls without a device (message via ws_last_error(NULL)). */
+int ws_validate_sgm(const ws_params *p, const ws_sgm_params *sgm, const ws_image *left, const ws_image *right);
+/* Host only: the device memory an SGM call with these arguments would hold. */
+int ws_sgm_scratch_bytes(const ws_params *p, const ws_sgm_params *sgm, const ws_image *left, const ws_image *right,
+                         unsigned long long *bytes);
+/* On device images into a float32 device map (out_stride floats per row).  Only enqueues, on `stream` (NULL = the
+ * context's own), like ws_search_device. */
+int ws_search_sgm_device(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *left_dev,
+                         const ws_image *right_dev, float *out_dev, int out_stride, void *stream);
+/* On host buffers, synchronous, as ws_search_host (the same staging path); F64 is the float32 map widened. */
+int ws_search_sgm_host(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *left,
+                       const ws_image *right, void *out, int out_stride, int out_dtype);
+
 /* ---- many pairs over the devices of a node ------------------------------------------------ */
 /*
  * Independent pairs are dealt to WORKERS: one ws_context and one host thread each.  Workers are device indices; a device

@@ -47,7 +47,8 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_rectified_size", "ws_rectify_device", "ws_search_unrectified_host",
            "ws_batch_create", "ws_batch_destroy", "ws_batch_last_error", "ws_batch_workers", "ws_batch_plan",
            "ws_batch_search_host", "ws_lr_check_device", "ws_search_lr_host", "ws_search_lr_device", "ws_last_lr_counts",
-           "ws_filter_speckles_device", "ws_filter_speckles_host", "ws_last_speckle_counts"]
+           "ws_filter_speckles_device", "ws_filter_speckles_host", "ws_last_speckle_counts",
+           "ws_validate_sgm", "ws_sgm_scratch_bytes", "ws_search_sgm_device", "ws_search_sgm_host"]
 JOB_NOT_RUN = 1  # ws_job.status of a job its worker never reached (WS_JOB_NOT_RUN)
 
 
@@ -91,6 +92,43 @@ def speckle_params(new_val=0.0, max_speckle_size=100, max_diff=1.0):
     """ws_speckle_params: regions of at most max_speckle_size pixels whose 4-neighbours differ by at most max_diff
     become new_val; pixels equal to new_val are blank (OpenCV's filterSpeckles)."""
     return _SpeckleParams(new_val, max_speckle_size, max_diff)
+
+
+class _SgmParams(ctypes.Structure):
+    _fields_ = [("paths", ctypes.c_int), ("p1", ctypes.c_int), ("p2", ctypes.c_int)]
+
+
+def sgm_params(paths=8, p1=0, p2=0):
+    """ws_sgm_params: 4 or 8 aggregation paths, the penalty p1 for a disparity change of 1 between path neighbours and
+    p2 >= p1 for a larger one, in window-cost units (semi-global matching; rules in include/ws_stereo.h)."""
+    return _SgmParams(paths, p1, p2)
+
+
+def _image_struct(a):
+    """A ws_image over an H x W x 3 uint8 array's rows (rows may be padded), without copying."""
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 or a.strides[2] != 1 or a.strides[1] != 3:
+        raise ValueError("expected an H x W x 3 uint8 (BGR) image with dense rows")
+    return _Image(a.ctypes.data, a.shape[1], a.shape[0], a.strides[0])
+
+
+def validate_sgm(params, left, right, paths=8, p1=0, p2=0):
+    """ws_validate_sgm on host images (H x W x 3 uint8): 0 or the WS_ERR_* status an SGM call would return."""
+    lib = load_library()
+    sp = sgm_params(paths, p1, p2)
+    return int(lib.ws_validate_sgm(ctypes.byref(params), ctypes.byref(sp), ctypes.byref(_image_struct(left)),
+                                   ctypes.byref(_image_struct(right))))
+
+
+def sgm_scratch_bytes(params, left, right, paths=8, p1=0, p2=0):
+    """ws_sgm_scratch_bytes: the device memory an SGM call on these images would hold (raises WsError if refused)."""
+    lib = load_library()
+    sp = sgm_params(paths, p1, p2)
+    n = ctypes.c_ulonglong()
+    rc = lib.ws_sgm_scratch_bytes(ctypes.byref(params), ctypes.byref(sp), ctypes.byref(_image_struct(left)),
+                                  ctypes.byref(_image_struct(right)), ctypes.byref(n))
+    if rc != 0:
+        raise WsError(rc, lib.ws_last_error(None).decode())
+    return int(n.value)
 
 
 class _Job(ctypes.Structure):
@@ -213,6 +251,10 @@ def load_library(build_if_missing=False):
     lib.ws_filter_speckles_device.argtypes = [vp, vp, ci, ci, ci, P(_SpeckleParams), vp]
     lib.ws_filter_speckles_host.argtypes = [vp, vp, ci, ci, ci, P(_SpeckleParams)]
     lib.ws_last_speckle_counts.argtypes = [vp, P(ctypes.c_ulonglong)]
+    lib.ws_validate_sgm.argtypes = [P(_Params), P(_SgmParams), P(_Image), P(_Image)]
+    lib.ws_sgm_scratch_bytes.argtypes = [P(_Params), P(_SgmParams), P(_Image), P(_Image), P(ctypes.c_ulonglong)]
+    lib.ws_search_sgm_device.argtypes = [vp, P(_Params), P(_SgmParams), P(_Image), P(_Image), vp, ci, vp]
+    lib.ws_search_sgm_host.argtypes = [vp, P(_Params), P(_SgmParams), P(_Image), P(_Image), vp, ci, ci]
     _lib = lib
     return lib
 
@@ -369,6 +411,34 @@ class WindowSearch:
         c = (ctypes.c_ulonglong * 2)()
         self._check(self._lib.ws_last_lr_counts(self._h, c))
         return int(c[0]), int(c[1])
+
+    # -- semi-global matching (extension; rules in include/ws_stereo.h) --------------------------
+    def search_sgm(self, params, left, right, paths=8, p1=0, p2=0, dtype=np.float64, out=None):
+        """ws_search_sgm_host: the view's map with the window costs aggregated along `paths` image paths (penalties
+        p1, p2).  `out` as for search()."""
+        La, Li = _host_image(left)
+        Ra, Ri = _host_image(right)
+        shape = La.shape[:2] if params.view == VIEW_LEFT else Ra.shape[:2]
+        if out is None:
+            out = np.empty(shape, dtype=dtype)
+        elif out.shape != shape or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("out must be a C-contiguous array of shape %s" % (shape,))
+        if out.dtype not in (np.float32, np.float64):
+            raise ValueError("dtype must be float32 or float64")
+        sp = sgm_params(paths, p1, p2)
+        self._check(self._lib.ws_search_sgm_host(self._h, ctypes.byref(params), ctypes.byref(sp), ctypes.byref(Li),
+                                                 ctypes.byref(Ri), out.ctypes.data, shape[1],
+                                                 OUT_F64 if out.dtype == np.float64 else OUT_F32))
+        return out
+
+    def search_sgm_device(self, params, left_t, right_t, out_t, paths=8, p1=0, p2=0, stream=None):
+        """ws_search_sgm_device on uint8 CUDA images and a float32 CUDA map (as search_device).  Only enqueues."""
+        Li = _Image(left_t.data_ptr(), left_t.shape[1], left_t.shape[0], left_t.stride(0))
+        Ri = _Image(right_t.data_ptr(), right_t.shape[1], right_t.shape[0], right_t.stride(0))
+        sp = sgm_params(paths, p1, p2)
+        self._check(self._lib.ws_search_sgm_device(self._h, ctypes.byref(params), ctypes.byref(sp), ctypes.byref(Li),
+                                                   ctypes.byref(Ri), out_t.data_ptr(), out_t.stride(0),
+                                                   ctypes.c_void_p(stream or 0)))
 
     # -- speckle filter (extension; rules in include/ws_stereo.h) ---------------------------------
     def filter_speckles(self, disparity, new_val=0.0, max_speckle_size=100, max_diff=1.0):

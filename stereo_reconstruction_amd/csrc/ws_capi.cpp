@@ -167,6 +167,7 @@ void ws_destroy(ws_context *ctx)
         if (e) (void)hipEventDestroy(e);
     if (ctx->lr.ev) (void)hipEventDestroy(ctx->lr.ev);
     if (ctx->speckle.ev) (void)hipEventDestroy(ctx->speckle.ev);
+    if (ctx->sgm.ev) (void)hipEventDestroy(ctx->sgm.ev);
     // every buffer goes with its owner, on this device, with nothing using it.  A batch never waited for: its maps are NOT
     // handed over -- only ws_wait delivers, and a caller who abandoned the batch may have freed the buffers they go to
     delete ctx;

@@ -1,5 +1,5 @@
 // ws_context.h -- the context behind the C-ABI's opaque ws_context, for the sources that implement its entry points
-// (ws_capi.cpp, ws_lr.cpp, ws_speckle.cpp), and the epilogue of their synchronous host calls.
+// (ws_capi.cpp, ws_lr.cpp, ws_speckle.cpp, ws_sgm.cpp), and the epilogue of their synchronous host calls.
 #pragma once
 
 #include "ws_capi_internal.h"
@@ -53,6 +53,16 @@ struct SpeckleState {
     bool ran = false;  // a filter was enqueued: counts_host holds (or will hold) its counts
 };
 
+// Semi-global matching's device memory (ws_sgm.cpp): the candidate intervals, the cost plane and the path sums of one
+// call, grown to what the call needs.  Shared by every SGM call of the context, with the same cross-stream wait as
+// LrState; the searches' own scratch (Searcher) is apart from it.
+struct SgmState {
+    DevBuf scratch;
+    hipEvent_t ev = nullptr; // end of the last SGM call
+    hipStream_t stream = nullptr;
+    bool busy = false; // ev is recorded on `stream`
+};
+
 } // namespace wsamd
 #pragma GCC visibility pop
 
@@ -62,6 +72,7 @@ struct ws_context {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // ws_timer_begin / ws_timer_end
     wsamd::Searcher searcher;                       // what only the searches touch (ws_search.h)
+    wsamd::SgmState sgm;                            // semi-global matching (ws_sgm.cpp)
     wsamd::DevBuf d_left, d_right, d_out, d_out64 /* the consumers' scratch */, d_out16;
     wsamd::DevBuf d_rect_left, d_rect_right; // ws_search_unrectified_host: the rectified images
     wsamd::DevBuf d_mesh, d_mesh_text;       // the mesh text (ws_mesh.hip): per-workgroup sums / offsets and the file's bytes

@@ -1,0 +1,211 @@
+// ws_sgm.cpp -- semi-global matching of include/ws_stereo.h (extension): argument checks, the storage widths from the
+// host's bound, the context's scratch for it (SgmState), and the launches of ws_sgm.hip on device memory or on the
+// caller's host buffers (through ws_staging.h).
+#include "ws_context.h"
+#include "ws_sgm.h"
+
+#include <stdint.h>
+
+#include <algorithm>
+
+namespace wsamd {
+namespace {
+
+// The disparities an SGM search looks at: what the geometry allows of the view's range (the candidate sets of all
+// pixels lie inside it).  Left view d = 1 .. min(maxD, w1 - 1 - 2 half); right view d = minD .. min(maxD, w1) - 1.
+void disparity_range(const ws_params *p, const ws_image *L, int *d0, int *nd)
+{
+    const int half = (p->block_size - 1) / 2;
+    if (p->view == WS_VIEW_LEFT) {
+        *d0 = 1;
+        *nd = std::max(0, std::min(p->max_disparity, L->width - 1 - 2 * half));
+    } else {
+        *d0 = p->min_disparity;
+        *nd = p->max_disparity <= p->min_disparity ? 0 : std::max(0, std::min(p->max_disparity, L->width) - p->min_disparity);
+    }
+}
+
+int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R)
+{
+    if (const int rc = check_params(err, p, L, R); rc != WS_OK) return rc;
+    if (p->view == WS_VIEW_LINEAR) return fail(err, WS_ERR_UNSUPPORTED, "SGM on LinearSearch");
+    if (p->smooth_factor != 1.0) return fail(err, WS_ERR_UNSUPPORTED, "SGM together with smoothFactor != 1");
+    if (p->view == WS_VIEW_RIGHT && p->var_block) return fail(err, WS_ERR_UNSUPPORTED, "SGM together with varBlock");
+    if (!sgm) return fail(err, WS_ERR_ARG, "null ws_sgm_params");
+    if (sgm->paths != 4 && sgm->paths != 8) return fail(err, WS_ERR_ARG, "paths %d: must be 4 or 8", sgm->paths);
+    if (sgm->p1 < 0) return fail(err, WS_ERR_ARG, "p1 %d: must be >= 0", sgm->p1);
+    if (sgm->p2 < sgm->p1) return fail(err, WS_ERR_ARG, "p2 %d: must be >= p1 (%d)", sgm->p2, sgm->p1);
+    int d0, nd;
+    disparity_range(p, L, &d0, &nd);
+    if (nd > kSgmMaxNd) return fail(err, WS_ERR_UNSUPPORTED, "SGM over %d disparities: at most %d", nd, kSgmMaxNd);
+    const int w = p->view == WS_VIEW_LEFT ? L->width : R->width, h = p->view == WS_VIEW_LEFT ? L->height : R->height;
+    if ((long long)w * h >= (1LL << 31)) return fail(err, WS_ERR_UNSUPPORTED, "SGM on a map of 2^31 pixels or more");
+    return WS_OK;
+}
+
+// The scratch of one call: the candidate intervals, the cost plane and the sums, each 256-byte aligned.  Storage
+// widths from the bound: C <= Cmax = 3 (255 or 255^2) bs^2 < 2^30; Lr <= C + P2 < 2^32; S <= paths (Cmax + P2).
+struct Layout {
+    int d0 = 0, nd = 0, w = 0, h = 0, cost16 = 0, sum64 = 0;
+    size_t off_cost = 0, off_sum = 0, bytes = 0;
+};
+
+Layout layout(const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R)
+{
+    Layout y;
+    disparity_range(p, L, &y.d0, &y.nd);
+    y.w = p->view == WS_VIEW_LEFT ? L->width : R->width;
+    y.h = p->view == WS_VIEW_LEFT ? L->height : R->height;
+    const uint64_t cmax = sgm_cost_max(p->cost == WS_COST_SSD, p->block_size);
+    y.cost16 = cmax <= 0xffffu;
+    y.sum64 = (uint64_t)sgm->paths * (cmax + (uint64_t)sgm->p2) > 0xffffffffull;
+    const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t px = (size_t)y.w * y.h, vol = px * (size_t)y.nd;
+    y.off_cost = up(px * 4);
+    y.off_sum = y.off_cost + up(vol * (y.cost16 ? 2 : 4));
+    y.bytes = y.off_sum + up(vol * (y.sum64 ? 8 : 4));
+    return y;
+}
+
+// Grown to exactly what the call needs (the volumes are large: no headroom).  A failed allocation leaves the context
+// without SGM scratch and usable.
+int sgm_ensure(ws_context *ctx, size_t bytes)
+{
+    DevBuf &b = ctx->sgm.scratch;
+    if (bytes <= b.cap) return WS_OK;
+    if (b.p) WS_HIP(&ctx->err, hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    if (hipMalloc(&b.p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return fail(&ctx->err, WS_ERR_NOMEM, "SGM scratch of %zu bytes could not be allocated", bytes);
+    }
+    b.cap = bytes;
+    return WS_OK;
+}
+
+// The context's SGM scratch on stream s: a call on another stream than the previous one first waits for it (on the
+// device), as the left-right check does (ws_lr.cpp).
+int sgm_acquire(ws_context *ctx, hipStream_t s)
+{
+    SgmState &S = ctx->sgm;
+    if (!S.ev) WS_HIP(&ctx->err, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+    if (S.busy && s != S.stream) WS_HIP(&ctx->err, hipStreamWaitEvent(s, S.ev, 0));
+    return WS_OK;
+}
+
+int sgm_release(ws_context *ctx, hipStream_t s)
+{
+    SgmState &S = ctx->sgm;
+    S.busy = false;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cap);
+    if (cap == hipStreamCaptureStatusNone) { // (an event recorded inside a capture cannot be waited for outside it)
+        WS_HIP(&ctx->err, hipEventRecord(S.ev, s));
+        S.busy = true;
+        S.stream = s;
+    }
+    return WS_OK;
+}
+
+// Scratch, then the kernels on s into out (out_stride floats per row).
+int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
+                int out_stride, hipStream_t s)
+{
+    const Layout y = layout(p, sgm, L, R);
+    int rc;
+    if ((rc = sgm_acquire(ctx, s)) != WS_OK) return rc;
+    // (a grown buffer is freed and allocated again: hipFree waits for the work still using the old one)
+    if ((rc = sgm_ensure(ctx, y.bytes)) != WS_OK) return rc;
+    SgmArgs a{};
+    a.L = L->data; a.R = R->data;
+    a.w1 = L->width; a.h1 = L->height; a.s1 = L->stride;
+    a.w2 = R->width; a.h2 = R->height; a.s2 = R->stride;
+    a.right = p->view == WS_VIEW_RIGHT;
+    a.ssd = p->cost == WS_COST_SSD;
+    a.half = (p->block_size - 1) / 2;
+    a.d0 = y.d0; a.nd = y.nd;
+    a.w = y.w; a.h = y.h;
+    a.p1 = (uint32_t)sgm->p1; a.p2 = (uint32_t)sgm->p2;
+    auto *base = static_cast<uint8_t *>(ctx->sgm.scratch.p);
+    a.kr = reinterpret_cast<uint32_t *>(base);
+    a.cost = base + y.off_cost;
+    a.sum = base + y.off_sum;
+    a.cost16 = y.cost16; a.sum64 = y.sum64;
+    a.subpixel = p->subpixel != 0;
+    a.out = out;
+    a.out_pitch = out_stride;
+    WS_HIP(&ctx->err, launch_sgm(a, sgm->paths, s));
+    return sgm_release(ctx, s);
+}
+
+} // namespace
+} // namespace wsamd
+
+using namespace wsamd;
+
+extern "C" {
+
+int ws_validate_sgm(const ws_params *p, const ws_sgm_params *sgm, const ws_image *left, const ws_image *right)
+{
+    return check_sgm(nullptr, p, sgm, left, right);
+}
+
+int ws_sgm_scratch_bytes(const ws_params *p, const ws_sgm_params *sgm, const ws_image *left, const ws_image *right,
+                         unsigned long long *bytes)
+{
+    if (!bytes) return fail(nullptr, WS_ERR_ARG, "null bytes");
+    if (const int rc = check_sgm(nullptr, p, sgm, left, right); rc != WS_OK) return rc;
+    *bytes = layout(p, sgm, left, right).bytes;
+    return WS_OK;
+}
+
+int ws_search_sgm_device(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *left_dev,
+                         const ws_image *right_dev, float *out_dev, int out_stride, void *stream)
+{
+    if (!ctx) return fail(nullptr, WS_ERR_ARG, "null context");
+    int rc = check_sgm(&ctx->err, p, sgm, left_dev, right_dev);
+    if (rc != WS_OK) return rc;
+    const int ow = p->view == WS_VIEW_LEFT ? left_dev->width : right_dev->width;
+    if (!out_dev) return fail(&ctx->err, WS_ERR_ARG, "null output");
+    if (out_stride < ow) return fail(&ctx->err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    return enqueue_sgm(ctx, p, sgm, left_dev, right_dev, out_dev, out_stride, s);
+}
+
+// As ws_search_host: both images up (through the shared staging path), the search on the context's stream into a dense
+// float32 map, and the map down, widened to the caller's type on the host.  One synchronisation at the end.
+int ws_search_sgm_host(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *left,
+                       const ws_image *right, void *out, int out_stride, int out_dtype)
+{
+    if (!ctx) return fail(nullptr, WS_ERR_ARG, "null context");
+    int ow, oh;
+    int rc = check_sgm(&ctx->err, p, sgm, left, right);
+    if (rc == WS_OK) rc = check_out(&ctx->err, p, left, right, out, out_stride, out_dtype, &ow, &oh);
+    if (rc != WS_OK) return rc;
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HostSpan sp[3];
+    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left))) != WS_OK) return rc;
+    if ((rc = ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right))) != WS_OK) return rc;
+    if ((rc = ensure(&ctx->err, ctx->d_out, (size_t)ow * oh * sizeof(float))) != WS_OK) return rc;
+    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    span_set(sp[2], out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)oh, &ctx->h_out);
+    spans_attach(sp, 3);
+    rc = [&]() -> int {
+        ws_image dl, dr;
+        WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
+        WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
+        float *map = static_cast<float *>(ctx->d_out.p);
+        if (const int r = enqueue_sgm(ctx, p, sgm, &dl, &dr, map, ow, s); r != WS_OK) return r;
+        WS_HIP(&ctx->err, span_download(sp[2], 0, (size_t)out_stride, map, (size_t)ow, (size_t)oh, kWireF32, esz, s));
+        return WS_OK;
+    }();
+    for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
+    ctx->last_wire = kWireF32;
+    return finish_host_call(ctx, rc, sp, 3, {s}, "SGM host call");
+}
+
+} // extern "C"

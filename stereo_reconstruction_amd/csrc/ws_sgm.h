@@ -1,0 +1,41 @@
+// ws_sgm.h -- semi-global matching on the device (ws_sgm.hip), for ws_sgm.cpp.  Internal; the rules are in
+// include/ws_stereo.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#pragma GCC visibility push(hidden)
+namespace wsamd {
+
+constexpr int kSgmMaxNd = 2048; // disparities a path wave keeps in registers (32 per lane)
+
+// One SGM search.  Disparity index j = 0 .. nd-1 stands for d = d0 + j.  The output map is w x h (the left image for
+// the left view, the right image for the right view); every per-pixel plane below is dense, w x h.
+struct SgmArgs {
+    const uint8_t *L, *R;
+    int w1, h1, s1, w2, h2, s2;
+    int right;  // 0: left view, 1: right view
+    int ssd;
+    int half;   // (block_size - 1) / 2
+    int d0, nd; // d = d0 + j for j < nd (nd already clipped to what the geometry allows)
+    int w, h;   // the map
+    uint32_t p1, p2;
+    uint32_t *kr;   // per pixel: node: lo | hi << 16 (hi > lo); no candidate: 0xffffffff; else 0
+    void *cost;     // C(p, j): w*h*nd of uint16 (cost16) or uint32, j innermost
+    void *sum;      // S(p, j): w*h*nd of uint32 (sum64 == 0) or uint64
+    int cost16, sum64;
+    int subpixel;
+    float *out;
+    int out_pitch;
+};
+
+// The largest window cost of a search (a square window of bs x bs pixels, three channels).
+inline uint64_t sgm_cost_max(int ssd, int block_size) { return 3ull * (ssd ? 65025ull : 255ull) * (uint64_t)block_size * block_size; }
+
+// The cost plane, the paths (`paths` 4 or 8, one launch each, summed in place in order on s) and the winner.
+hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s);
+
+} // namespace wsamd
+#pragma GCC visibility pop

@@ -165,7 +165,27 @@ public:
         return out;
     }
 
+    // Extension: semi-global matching over the window costs of computeDisparityMapLeft(1) / computeDisparityMapRight(1)
+    // (rules in ws_stereo.h): P1 and P2 in cost units, 4 or 8 paths.  With P1 = P2 = 0 the maps are those two calls'.
+    MatF64 computeDisparityMapLeftSGM(int P1, int P2, int paths = 8) { return sgm(WS_VIEW_LEFT, P1, P2, paths); }
+    MatF64 computeDisparityMapRightSGM(int P1, int P2, int paths = 8) { return sgm(WS_VIEW_RIGHT, P1, P2, paths); }
+
 private:
+    MatF64 sgm(int view, int P1, int P2, int paths)
+    {
+        const ws_params p = params(view, 1.0);
+        ws_sgm_params sp;
+        sp.paths = paths;
+        sp.p1 = P1;
+        sp.p2 = P2;
+        const bool left = view == WS_VIEW_LEFT;
+        MatF64 out(left ? leftImage_.rows : rightImage_.rows, left ? leftImage_.cols : rightImage_.cols);
+        const ws_image li = detail::to_c(leftImage_), ri = detail::to_c(rightImage_);
+        const int rc = ws_search_sgm_host(device_.get(), &p, &sp, &li, &ri, out.ptr(), out.cols, WS_OUT_F64);
+        if (rc != WS_OK) throw Error(rc, ws_last_error(device_.get()));
+        return out;
+    }
+
     ws_params params(int view, double smoothFactor) const
     {
         ws_params p;
