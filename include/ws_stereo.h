@@ -494,6 +494,27 @@ int ws_last_wire_format(const ws_context *ctx, int *wire);
  * alone, and the double one ran after it.  The results are identical; for tests and reports.
  */
 int ws_last_outliers_path(const ws_context *ctx, int *path);
+/*
+ * Which form of those kernels the last ws_remove_disparity_outliers call launched, recorded by the launchers at the
+ * launch: integer_pass for the 32-bit integer box filter, double_pass for the double-precision one (both are filled
+ * when ws_last_outliers_path is 2; a pass that did not run is all zeros).
+ *   row_kernel  0 = not launched, 1 = 32-bit integer rows, 2 = double rows with the row's prefix in LDS,
+ *               3 = the direct O(kernel_size) rows (width > 5458)
+ *   row_passes  trips of the row kernel's loading loop: 4096 pixels a trip for 1, 2048 for 2, 0 for 3
+ *   row_per     pixels per thread of row kernel 2's scan, ceil(width / 256); 0 for the others
+ *   col_band    columns per workgroup of the column kernel (integer: 4, 8, 16; double: 2, 4, 8, 16);
+ *               0 = the direct O(kernel_size) columns (double only, height > 9087)
+ *   row_window  1 = short (kernel_size <= width: the window reflects once at most), 2 = periodic
+ *   col_window  the same for kernel_size and height
+ * The results do not depend on the form; for tests and reports.
+ */
+typedef struct ws_outliers_pass {
+    int row_kernel, row_passes, row_per, col_band, row_window, col_window;
+} ws_outliers_pass;
+typedef struct ws_outliers_forms {
+    ws_outliers_pass integer_pass, double_pass;
+} ws_outliers_forms;
+int ws_last_outliers_forms(const ws_context *ctx, ws_outliers_forms *forms);
 
 /* ---- Middlebury plumbing around the path ------------------------------------------ */
 /*

@@ -42,7 +42,7 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_warp_nearest_device", "ws_remove_disparity_outliers", "ws_convert_disparity_to_depth",
            "ws_back_project", "ws_write_mesh_off", "ws_write_mesh_off_device", "ws_reconstruction_host",
            "ws_timer_begin", "ws_timer_end", "ws_set_profiling", "ws_last_kernel_ms",
-           "ws_last_launch_info", "ws_last_max_block", "ws_set_tuning", "ws_set_host_bands", "ws_last_host_paths", "ws_last_wire_format", "ws_last_outliers_path", "ws_device_status",
+           "ws_last_launch_info", "ws_last_max_block", "ws_set_tuning", "ws_set_host_bands", "ws_last_host_paths", "ws_last_wire_format", "ws_last_outliers_path", "ws_last_outliers_forms", "ws_device_status",
            "ws_pfm_read", "ws_pfm_write", "ws_free", "ws_ppm_read", "ws_ppm_write", "ws_calib_read", "ws_evaldisp",
            "ws_rectified_size", "ws_rectify_device", "ws_search_unrectified_host",
            "ws_batch_create", "ws_batch_destroy", "ws_batch_last_error", "ws_batch_workers", "ws_batch_plan",
@@ -69,6 +69,14 @@ class _Params(ctypes.Structure):
                 ("smooth_factor", ctypes.c_double), ("var_block", ctypes.c_int),
                 ("thres", ctypes.c_double), ("subpixel", ctypes.c_int),
                 ("linear_range", ctypes.c_int)]
+
+
+class _OutliersPass(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("row_kernel", "row_passes", "row_per", "col_band", "row_window", "col_window")]
+
+
+class _OutliersForms(ctypes.Structure):
+    _fields_ = [("integer_pass", _OutliersPass), ("double_pass", _OutliersPass)]
 
 
 class _LrParams(ctypes.Structure):
@@ -222,6 +230,7 @@ def load_library(build_if_missing=False):
     lib.ws_last_host_paths.argtypes = [vp, P(ci)]
     lib.ws_last_wire_format.argtypes = [vp, P(ci)]
     lib.ws_last_outliers_path.argtypes = [vp, P(ci)]
+    lib.ws_last_outliers_forms.argtypes = [vp, P(_OutliersForms)]
     lib.ws_device_status.argtypes = [vp, vp]
     lib.ws_pfm_read.argtypes = [ctypes.c_char_p, P(P(ctypes.c_float)), P(ci), P(ci)]
     lib.ws_pfm_write.argtypes = [ctypes.c_char_p, vp, ci, ci, ci]
@@ -474,6 +483,16 @@ class WindowSearch:
                                                    m, out.ctypes.data, out.shape[1], out.shape[0], out.shape[1]))
         return out
 
+    def warp_nearest_device(self, src_t, matrix, dst_t, stream=None):
+        """ws_warp_nearest_device: the same warp between float32 CUDA maps (H x W, rows may be padded).  Only enqueues on
+        `stream`, a hipStream_t handle (None or 0: the context's own NON-BLOCKING stream, see rectify_device)."""
+        for t in (src_t, dst_t):
+            if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.element_size() != 4 or not t.is_floating_point():
+                raise ValueError("expected a float32 H x W CUDA tensor with dense rows")
+        self._check(self._lib.ws_warp_nearest_device(self._h, src_t.data_ptr(), src_t.shape[1], src_t.shape[0],
+                                                     src_t.stride(0), _mat9(matrix), dst_t.data_ptr(), dst_t.shape[1],
+                                                     dst_t.shape[0], dst_t.stride(0), ctypes.c_void_p(stream or 0)))
+
     # -- rectification (rectification.cpp:432-505, :66-88) ----------------------------------
     def rectify_device(self, src_t, H, dst_t, stream=None):
         """ws_rectify_device: cv::warpPerspective(src, dst, H, dst.size()) -- INTER_LINEAR, BORDER_CONSTANT 0 -- on
@@ -612,6 +631,22 @@ class WindowSearch:
         v = ctypes.c_int(0)
         self._check(self._lib.ws_last_outliers_path(self._h, ctypes.byref(v)))
         return ("double", "integer", "integer-then-double")[v.value]
+
+    def last_outliers_forms(self):
+        """ws_last_outliers_forms: which kernel forms the last remove_disparity_outliers launched, as
+        {'integer': pass or None, 'double': pass or None}; a pass is {'rows': 'u32' / 'lds-prefix' / 'direct',
+        'row_passes', 'row_per', 'cols': the band width or 'direct', 'row_window', 'col_window': 'short' / 'periodic'}."""
+        f = _OutliersForms()
+        self._check(self._lib.ws_last_outliers_forms(self._h, ctypes.byref(f)))
+
+        def one(p):
+            if not p.row_kernel:
+                return None
+            return {"rows": (None, "u32", "lds-prefix", "direct")[p.row_kernel], "row_passes": p.row_passes,
+                    "row_per": p.row_per, "cols": p.col_band or "direct",
+                    "row_window": (None, "short", "periodic")[p.row_window],
+                    "col_window": (None, "short", "periodic")[p.col_window]}
+        return {"integer": one(f.integer_pass), "double": one(f.double_pass)}
 
     def set_host_bands(self, bands=-1):
         self._check(self._lib.ws_set_host_bands(self._h, bands))

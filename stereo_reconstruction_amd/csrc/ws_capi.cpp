@@ -313,6 +313,22 @@ int ws_last_outliers_path(const ws_context *ctx, int *path)
     return WS_OK;
 }
 
+int ws_last_outliers_forms(const ws_context *ctx, ws_outliers_forms *forms)
+{
+    if (!ctx || !forms) return WS_ERR_ARG;
+    for (int i = 0; i < 2; ++i) {
+        const OutlierForms &f = ctx->last_outliers_forms[i];
+        ws_outliers_pass &o = i == 0 ? forms->integer_pass : forms->double_pass;
+        o.row_kernel = f.row_kernel;
+        o.row_passes = f.row_passes;
+        o.row_per = f.row_per;
+        o.col_band = f.col_band;
+        o.row_window = f.row_window;
+        o.col_window = f.col_window;
+    }
+    return WS_OK;
+}
+
 int ws_set_host_bands(ws_context *ctx, int bands)
 {
     if (!ctx || bands < -1 || bands > ws_context::kMaxBands) return WS_ERR_ARG;
@@ -683,12 +699,15 @@ int ws_remove_disparity_outliers(ws_context *ctx, float *map, int width, int hei
     // 8-bit maps (the pipeline's PNG: integers in [0, 255]) take the 32-bit integer kernels; a map with any other value
     // raises status word 1, is left as uploaded, and goes through the double kernels after the first synchronisation
     const bool try_u32 = ctx->d_flag.p && outliers_u32_applies(width, height, kernel_size, ctx->num_cus);
+    ctx->last_outliers_forms[0] = ctx->last_outliers_forms[1] = OutlierForms{};
     auto pass = [&](bool u32) -> int { // the kernels on the uploaded map, the result down to the caller's
         if (u32)
             WS_HIP(&ctx->err, launch_outliers_u32(dmap, width, width, height, kernel_size, thr_front, thr_back, static_cast<uint32_t *>(ctx->d_out64.p),
-                                            static_cast<uint32_t *>(ctx->d_flag.p), ctx->status_dev + 1, ctx->num_cus, s));
+                                            static_cast<uint32_t *>(ctx->d_flag.p), ctx->status_dev + 1, ctx->num_cus, s,
+                                            &ctx->last_outliers_forms[0]));
         else
-            WS_HIP(&ctx->err, launch_outliers(dmap, width, width, height, kernel_size, thr_front, thr_back, static_cast<double *>(ctx->d_out64.p), s));
+            WS_HIP(&ctx->err, launch_outliers(dmap, width, width, height, kernel_size, thr_front, thr_back, static_cast<double *>(ctx->d_out64.p), s,
+                                        &ctx->last_outliers_forms[1]));
         WS_HIP(&ctx->err, span_download_bytes(sp[0], 0, (size_t)stride * 4, dmap, (size_t)width * 4, (size_t)height, s));
         return WS_OK;
     };

@@ -225,7 +225,8 @@ __global__ void __launch_bounds__(1024) ws_outlier_cols_kernel(const double *__r
     }
 }
 
-// the literal O(k) form: lines too long for the LDS prefix (rows beyond 8190 pixels, columns beyond ~9500)
+// the literal O(k) form: lines too long for the LDS prefix (launch_outliers: rows beyond 5458 pixels -- 12 bytes a
+// pixel of the 64 KB a row's workgroup takes --, columns beyond 9087 -- 32 rows a thread of the 2-column band)
 __global__ void __launch_bounds__(256) ws_box_rows_direct_kernel(const float *__restrict__ src, int sp, double *__restrict__ dst,
                                                                  int dp, int w, int h, int k)
 {
@@ -502,7 +503,7 @@ bool outliers_u32_applies(int w, int h, int k, int num_cus)
 }
 
 hipError_t launch_outliers_u32(float *map, int mp, int w, int h, int k, float thr_front, float thr_back, uint32_t *scratch,
-                               uint32_t *flag, unsigned int *host_word, int num_cus, hipStream_t s)
+                               uint32_t *flag, unsigned int *host_word, int num_cus, hipStream_t s, OutlierForms *forms)
 {
     const int bw = outliers_u32_band(w, h, num_cus);
     if (!bw || !outliers_u32_applies(w, h, k, num_cus)) return hipErrorInvalidValue;
@@ -513,11 +514,19 @@ hipError_t launch_outliers_u32(float *map, int mp, int w, int h, int k, float th
     hipLaunchKernelGGL(ws_box_rows_u32_kernel<256>, dim3(h), dim3(256), row_lds, s, map, mp, scratch, w, h, k, lb, flag, host_word);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (forms) {
+        forms->row_kernel = 1;
+        forms->row_passes = ceil_div(w, kRowPer * 256);
+        forms->row_per = 0;
+        forms->row_window = k <= w ? 1 : 2;
+        forms->col_window = k <= h ? 1 : 2;
+    }
     auto launch = [&](auto kernel) -> hipError_t {
         const size_t lds = (size_t)(h + 1 + 16) * bw * sizeof(uint32_t);
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) return err;
         hipLaunchKernelGGL(kernel, dim3(ceil_div(w, bw)), dim3(1024), lds, s, scratch, map, mp, w, h, k, thr_front, thr_back, flag);
+        if (forms) forms->col_band = bw;
         return hipGetLastError();
     };
     if (bw == 16) return launch(ws_outlier_cols_u32_kernel<16, 1024>);
@@ -526,15 +535,29 @@ hipError_t launch_outliers_u32(float *map, int mp, int w, int h, int k, float th
 }
 
 hipError_t launch_outliers(float *map, int mp, int w, int h, int k, float thr_front, float thr_back, double *scratch,
-                           hipStream_t s)
+                           hipStream_t s, OutlierForms *forms)
 {
     constexpr size_t kLdsBudget = 150 * 1024;
+    if (forms) {
+        forms->row_window = k <= w ? 1 : 2;
+        forms->col_window = k <= h ? 1 : 2;
+    }
     // rows: one workgroup per row with the row's prefix in LDS
     const size_t row_lds = (size_t)(w + 1 + 4) * sizeof(double) + (size_t)w * sizeof(float);
     if (row_lds <= 64 * 1024) {
         hipLaunchKernelGGL(ws_box_rows_kernel, dim3(h), dim3(256), row_lds, s, map, mp, scratch, w, w, h, k);
+        if (forms) {
+            forms->row_kernel = 2;
+            forms->row_passes = ceil_div(w, 8 * 256);
+            forms->row_per = ceil_div(w, 256);
+        }
     } else {
         hipLaunchKernelGGL(ws_box_rows_direct_kernel, dim3(ceil_div(w, 256), h), dim3(256), 0, s, map, mp, scratch, w, w, h, k);
+        if (forms) {
+            forms->row_kernel = 3;
+            forms->row_passes = 0;
+            forms->row_per = 0;
+        }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -548,15 +571,17 @@ hipError_t launch_outliers(float *map, int mp, int w, int h, int k, float thr_fr
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) return err;
         hipLaunchKernelGGL(kernel, dim3(ceil_div(w, bw)), dim3(1024), lds, s, scratch, w, map, mp, w, h, k, thr_front, thr_back);
+        if (forms) forms->col_band = bw;
         return hipGetLastError();
     };
-    // (narrower bands when the wide ones would leave most CUs without a workgroup)
+    // (narrower bands when the wide ones would leave most CUs without a workgroup.  Whatever fits 16 fits 8 -- half
+    // the LDS, half the rows a thread -- so 16 is taken by the first line or not at all)
     if (fits(16) && ceil_div(w, 16) >= 200) return launch(ws_outlier_cols_kernel<16>, 16);
     if (fits(8)) return launch(ws_outlier_cols_kernel<8>, 8);
-    if (fits(16)) return launch(ws_outlier_cols_kernel<16>, 16);
     if (fits(4)) return launch(ws_outlier_cols_kernel<4>, 4);
     if (fits(2)) return launch(ws_outlier_cols_kernel<2>, 2);
     hipLaunchKernelGGL(ws_outlier_direct_kernel, dim3(ceil_div(w, 256), h), dim3(256), 0, s, scratch, w, map, mp, w, h, k, thr_front, thr_back);
+    if (forms) forms->col_band = 0;
     return hipGetLastError();
 }
 

@@ -88,6 +88,7 @@ struct ws_context {
     unsigned int *status_host = nullptr, *status_dev = nullptr; // mapped pinned words the kernels flag trouble in (word 0: ws_smooth_left_bands_kernel gave up; word 1: the integer box filter met a value it cannot carry)
     wsamd::DevBuf d_flag;                     // 256 bytes: word 0 = the integer box filter met a value it cannot carry
     int last_outliers_path = 0;        // ws_last_outliers_path
+    wsamd::OutlierForms last_outliers_forms[2]; // ws_last_outliers_forms: what the integer / the double launcher launched
     int last_how[3] = {0, 0, 0};       // ws_last_host_paths: how the last host call's left / right / out bytes crossed
     int last_wire = 0;                 // ... and the wire format of its map (ws_last_wire_format)
     std::vector<wsamd::HostSpan> batch_spans; // caller buffers of the pairs enqueued since the last ws_wait (released there)

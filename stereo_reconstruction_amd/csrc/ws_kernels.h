@@ -122,16 +122,26 @@ hipError_t launch_smooth(const GenericArgs &g, double s, uint8_t *sel, int sel_p
 // nearest-neighbour perspective warp of a float map; minv maps destination -> source pixels
 hipError_t launch_warp(const float *src, int sw, int sh, int sp, float *dst, int dw, int dh, int dp,
                        const double minv[9], hipStream_t s);
+// What one launcher of the box filter launched, written by the launcher at the launch from the values it launches with
+// (ws_last_outliers_forms; the codes are those of ws_outliers_forms in include/ws_stereo.h).
+struct OutlierForms {
+    int row_kernel = 0; // 0 = not launched, 1 = 32-bit integer rows, 2 = double rows with the prefix in LDS, 3 = direct O(k) rows
+    int row_passes = 0; // trips of the row kernel's loading loop (0 for the direct kernel)
+    int row_per = 0;    // pixels per thread of the LDS-prefix row kernel's scan (0 for the others)
+    int col_band = 0;   // columns per workgroup of the column kernel; 0 = the direct O(k) column kernel
+    int row_window = 0; // 1 = short (k <= w: one reflection at most), 2 = periodic (k > w)
+    int col_window = 0; // the same for k and h
+};
 // removeDisparityOutliers (reconstruction.cpp:5-18); scratch = w*h doubles
 hipError_t launch_outliers(float *map, int mp, int w, int h, int k, float thr_front, float thr_back, double *scratch,
-                           hipStream_t s);
+                           hipStream_t s, OutlierForms *forms = nullptr);
 // the same for 8-bit maps (what the pipeline feeds it: an 8-bit PNG), all sums in 32-bit integers.  A map with any
 // value that is not an integer in [0, 255] sets *flag (device word, zero on entry) and *host_word (mapped host word)
 // and is left untouched: the caller then runs launch_outliers.  scratch = outliers_u32_scratch_bytes(w, h) bytes.
 bool outliers_u32_applies(int w, int h, int k, int num_cus);
 size_t outliers_u32_scratch_bytes(int w, int h, int num_cus);
 hipError_t launch_outliers_u32(float *map, int mp, int w, int h, int k, float thr_front, float thr_back, uint32_t *scratch,
-                               uint32_t *flag, unsigned int *host_word, int num_cus, hipStream_t s);
+                               uint32_t *flag, unsigned int *host_word, int num_cus, hipStream_t s, OutlierForms *forms = nullptr);
 // convertDisparityToDepth + back-projection (reconstruction.cpp:30-43, :152-196); depth / pos+col may be null
 hipError_t launch_depth_vertices(const float *disp, int dp, int w, int h, float focal, float baseline, const float k[9],
                                  const uint8_t *bgr, int bstride, float *depth, int zp, float *pos, uint8_t *col,
