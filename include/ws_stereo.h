@@ -115,6 +115,8 @@ typedef struct {
     int interior_x0, interior_x1, interior_y0, interior_y1; /* outputs the marching kernel writes */
     int passes;                     /* d-group passes (disparity ranges wider than one tile holds) */
     int tile_cols;                  /* columns a tile hands out: x_runs*x_per_thread, one run less for the halo-exchange SAD kernels */
+    int kernel_kind;                /* 0: the stencil marching kernel; 1: the int8 matrix-core SSD kernel (a wave owns 32 columns:
+                                       x_runs*x_per_thread is still the tile's width, d_chunks*d_per_thread the candidates a tile holds) */
 } ws_plan_info;
 int ws_plan(const ws_params *p, const ws_image *left, const ws_image *right, int num_cus,
             ws_plan_info *out);

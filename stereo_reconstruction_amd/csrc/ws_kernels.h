@@ -48,6 +48,8 @@ struct MarchLaunch {
     int tile_cols;                   // output columns per tile
     size_t lds_bytes;
     int max_threads;                 // launch-bounds variant (1024 or 768)
+    int mfma;                        // 1: the int8 matrix-core SSD kernel (ws_march_mfma.hip) runs this plan; the fields above
+                                     // then describe its tile in the stencil kernel's terms (32 runs of 8 columns, 32 chunks of 8 d)
 };
 
 // Which (window, X, ND) instantiations exist.  Returns false if none fits.
@@ -74,6 +76,13 @@ hipError_t launch_march(const Canon &c, const MarchLaunch &m, const uint8_t *img
                         int32_t *cost_out, int cost_pitch,
                         hipStream_t s); // cost_out: optional plane of the winners' costs (SSD: without sum a^2); out16: see GenericArgs
 const char *march_kernel_name(const Canon &c, const MarchLaunch &m);
+// The SSD search on the int8 matrix cores (ws_march_mfma.hip): plain bytes, left view, one d-group pass of up to 256
+// candidates, a window it is instantiated for, and a search big enough to fill the chip with its 256-column tiles.
+// march_mfma_plan fills the plan if the search is one of those (march_plan asks it when nothing is tuned by hand).
+bool march_mfma_plan(const Canon &c, int num_cus, MarchLaunch *out);
+const char *march_mfma_kernel_name(const Canon &c);
+hipError_t launch_march_mfma(const Canon &c, const MarchLaunch &m, const uint8_t *img_a, int stride_a, const uint8_t *img_b, int stride_b,
+                             float *out, int16_t *out16, int out_pitch, int border, int out_w, int out_h, hipStream_t s);
 bool march_has_cost(const Canon &c); // is there an instantiation that also writes cost_out?
 
 // Brute-force kernels on the original 8-bit images (original coordinates, literal rules).

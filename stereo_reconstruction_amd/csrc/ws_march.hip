@@ -31,8 +31,9 @@
 //                    and LinearSearch ranges beyond 4096.
 //   ws_refine_*      sub-pixel parabola (extension).
 //
-// No MFMA: the hot loop is a stencil + reduction on bytes, bounded by VALU issue and LDS, see
-// DESIGN.md.  Wave64 throughout; nothing here assumes 32-wide warps.
+// No MFMA in this kernel: its hot loop is a stencil + reduction on bytes, bounded by VALU issue and LDS, see
+// DESIGN.md (the SSD searches whose cross term runs on the matrix cores: ws_march_mfma.hip).  Wave64 throughout;
+// nothing here assumes 32-wide warps.
 #include "ws_march_kernel.h"
 
 #include <string.h>
@@ -260,7 +261,8 @@ bool march_plan(const Canon &c, int num_cus, int tune_nxr, int tune_strip_rows, 
     }();
     if (tune_threads <= 0 && env_threads >= 64) tune_threads = env_threads;
     if (!march_plan_threads(c, num_cus, tune_nxr, tune_strip_rows, tune_threads, out)) return false;
-    if (tune_threads > 0 || tune_nxr > 0 || tune_strip_rows > 0) return true;
+    if (tune_threads > 0 || tune_nxr > 0 || tune_strip_rows > 0) return true; // (a forced tuning means the stencil kernel)
+    if (march_mfma_plan(c, num_cus, out)) return true;
     MarchLaunch half{};
     // (halo-exchange plans trade d-group passes for runs per tile: their passes run back to back and count as rounds,
     // and the smaller workgroup has more of them by construction.  Config 3, 512 -> 256 threads: 3.94 -> 4.13 * 10^6
@@ -417,6 +419,7 @@ void march_plane_geometry(const Canon &c, const MarchLaunch &m, Plane *a, Plane 
 
 const char *march_kernel_name(const Canon &c, const MarchLaunch &m)
 {
+    if (m.mfma) return march_mfma_kernel_name(c);
     const MarchEntry *e = m.halo ? find_march_halo(c) : find_march(c);
     return e ? e->name : "";
 }
@@ -425,6 +428,10 @@ hipError_t launch_march(const Canon &c, const MarchLaunch &m, const uint8_t *img
                         float *out, int16_t *out16, int out_pitch, int border, int out_w, int out_h, void *keys, int keys_pitch,
                         int32_t *cost_out, int cost_pitch, hipStream_t s)
 {
+    if (m.mfma) {
+        if (cost_out || m.passes != 1) return hipErrorInvalidValue;
+        return launch_march_mfma(c, m, img_a, stride_a, img_b, stride_b, out, out16, out_pitch, border, out_w, out_h, s);
+    }
     const MarchEntry *e = m.halo ? find_march_halo(c) : find_march(c);
     if (!e) return hipErrorInvalidValue;
     MarchArgs g{};
