@@ -3,7 +3,7 @@ CPU reference (oracle.fast_left), np.array_equal.  Every case asserts that the m
 stencil kernel:
 
   * config 2's shape; max_disparity 33 / 100 / 255 / 256 (partial first and last tiles of target centres, the poisoned
-    triangles of candidates outside the range) and a width below max_disparity + the window (d clamped by the width);
+    triangles of candidates outside the range) and the narrowest search the selection rule gives the kernel;
   * widths and heights, found by scanning ws_plan, that put the image edge 1 and tile - 1 columns / 1 and strip - 1 rows
     past a seam;
   * inputs where only the tie tags decide (constant, constant_apart, extremes, saturated, periodic) and the maximum-cost
@@ -67,9 +67,10 @@ def test_disparity_ranges(wslib, gpu_ctx, oracle, maxd):
     _run(wslib, gpu_ctx, oracle, left, right, maxd, ("maxd", maxd))
 
 
-def test_d_clamped_by_the_width(wslib, gpu_ctx, oracle):
-    """The narrowest search the selection rule still gives the kernel, with max_disparity beyond width - window: the
-    candidate range is clamped by the geometry, most target centres of the first tiles lie outside the image."""
+def test_narrowest_selected_search(wslib, gpu_ctx, oracle):
+    """The narrowest search the selection rule still gives the kernel: of all the searches it sees, the one with the
+    most target centres of its first tiles outside the image.  (The clamp of the candidate range by the width,
+    d_hi = width - 7, cannot be reached: the rule needs 390 columns, max_disparity + the window is at most 262.)"""
     found = None
     for w in range(200, 700):
         for h in (200, 260, 400):
@@ -80,8 +81,6 @@ def test_d_clamped_by_the_width(wslib, gpu_ctx, oracle):
             break
     assert found, "no search narrower than 700 columns selects the matrix kernel"
     w, h = found
-    # (where the selection rule's narrowest search is still wider than max_disparity + the window, the range is not clamped;
-    # the narrowest search then has the most target centres outside the image the kernel ever sees)
     left, right, _ = make_pair(w, h, 256, 77)
     _run(wslib, gpu_ctx, oracle, left, right, 256, ("narrowest", w, h))
 
