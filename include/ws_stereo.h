@@ -106,7 +106,8 @@ int ws_device_count(void);
  */
 int ws_validate(const ws_params *p, const ws_image *left, const ws_image *right);
 
-/* How a search would be tiled on a device with num_cus compute units (0 = 256); host logic only. */
+/* How a search would be tiled on a device with num_cus compute units (0 = 256); host logic only.  Everything in the
+ * plan is for that chip: the thread shape (x_per_thread, d_per_thread) as well as the tiles and strips. */
 typedef struct {
     int marching;                   /* 1: the marching kernel owns the interior; 0: brute force only */
     int x_per_thread, d_per_thread; /* columns x disparities whose window sums one thread keeps */

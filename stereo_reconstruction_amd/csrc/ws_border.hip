@@ -303,7 +303,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     }
 }
 
-hipError_t launch_ring(const Canon &c, Plane a, Plane b, const GenericArgs &skip, float *out, int out_pitch,
+hipError_t launch_ring(const Canon &c, const MarchLaunch &m, Plane a, Plane b, const GenericArgs &skip, float *out, int out_pitch,
                        int32_t *cost_out, int cost_pitch, hipStream_t s)
 {
     RingArgs g{};
@@ -313,7 +313,7 @@ hipError_t launch_ring(const Canon &c, Plane a, Plane b, const GenericArgs &skip
     g.height = std::min(c.ha, c.hb);
     g.half = c.wh / 2; // right view: window (bs-1)^2 = (2*half)^2
     g.boff = c.boff; g.d_lo = c.d_lo; g.d_hi = c.d_hi_clipped;
-    g.ssd = c.ssd; g.centred = march_centred(c);
+    g.ssd = c.ssd; g.centred = m.centred;
     g.skip_x0 = skip.skip_x0; g.skip_x1 = skip.skip_x1; g.skip_y0 = skip.skip_y0; g.skip_y1 = skip.skip_y1;
     if (g.skip_x1 <= g.skip_x0 || g.skip_y1 <= g.skip_y0) { // no interior: every row is a "top" row
         g.skip_x0 = g.skip_x1 = 0;
@@ -526,7 +526,7 @@ __global__ void __launch_bounds__(256) ws_refine_planes_kernel(const RefineArgs 
     if (den > 0) *o = *o + (float)((double)num / (2.0 * (double)den));
 }
 
-hipError_t launch_refine_planes(const Canon &c, const MarchLaunch &, Plane a, Plane b, float *out, int out_pitch, hipStream_t s)
+hipError_t launch_refine_planes(const Canon &c, const MarchLaunch &m, Plane a, Plane b, float *out, int out_pitch, hipStream_t s)
 {
     RefineArgs g{};
     g.A = a.data; g.B = b.data;
@@ -534,7 +534,7 @@ hipError_t launch_refine_planes(const Canon &c, const MarchLaunch &, Plane a, Pl
     g.wa = c.wa; g.ww = c.ww; g.wh = c.wh; g.wx0 = c.wx0; g.wy0 = c.wy0; g.boff = c.boff;
     g.d_lo = c.d_lo; g.d_hi = c.d_hi; g.b_lo = c.b_lo; g.b_hi = c.b_hi;
     g.ox0 = c.ox0; g.ox1 = c.ox1; g.oy0 = c.oy0; g.oy1 = c.oy1;
-    g.ssd = c.ssd; g.centred = march_centred(c); g.mirror = c.mirror;
+    g.ssd = c.ssd; g.centred = m.centred; g.mirror = c.mirror;
     g.out = out; g.out_pitch = out_pitch;
     dim3 grid(ceil_div(c.ox1 - c.ox0, 256), c.oy1 - c.oy0);
     // (the window widths of the BASELINE configs with the sub-pixel extension get the compile-time form)

@@ -38,6 +38,12 @@ struct Plane {
     int pad;   // plane column = image column + pad
 };
 
+struct MarchArgs;
+typedef void (*MarchFn)(const MarchArgs); // a marching kernel (ws_march_kernel.h)
+
+// The plan of one marching search: the tiling AND the decision which kernel runs it.  march_plan takes that decision
+// once; the launcher launches what the plan names, and everything that reads the packed planes afterwards (pack, border
+// ring, refine, smoothFactor passes) takes `centred` from here -- nothing works it out again from the Canon.
 struct MarchLaunch {
     int x_per_thread, nd_per_thread; // X, ND template choice
     int nxr, nch;                    // x-runs per tile, d-chunks per tile (and pass)
@@ -50,15 +56,15 @@ struct MarchLaunch {
     int max_threads;                 // launch-bounds variant (1024 or 768)
     int mfma;                        // 1: the int8 matrix-core SSD kernel (ws_march_mfma.hip) runs this plan; the fields above
                                      // then describe its tile in the stencil kernel's terms (32 runs of 8 columns, 32 chunks of 8 d)
+    MarchFn fn, fn_cost;             // the instantiation that runs; fn_cost: its twin that also writes the winners' costs, or null
+    const char *name;                // ... as ws_last_launch_info reports it
+    int centred;                     // 1: this SSD window's packed planes hold centred (byte - 128) pixels to keep its sums in 32 bits
+                                     // (a matrix-kernel plan keeps the stencil plan's value: the planes do not depend on the kernel)
+    int tag_bits;                    // SAD: keys are (cost << tag_bits) | global tie tag (0 for the matrix kernel: it has none)
 };
 
-// Which (window, X, ND) instantiations exist.  Returns false if none fits.
-bool march_supported(const Canon &c);
-// 1 if this SSD window needs centred (byte - 128) planes to keep its sums in 32 bits
-int march_centred(const Canon &c);
-// The CU count the thread-shape rule (march_shape) plans for; ws_create passes its device's.
-void march_set_num_cus(int n);
-// Fill the tiling for this problem (tuning values of 0 = automatic).
+// Fill the plan for this problem on a chip of num_cus CUs (tuning values of 0 = automatic).  Returns false if no
+// (window, X, ND) instantiation fits.
 bool march_plan(const Canon &c, int num_cus, int tune_nxr, int tune_strip_rows, int tune_threads,
                 MarchLaunch *out);
 // Plane geometry (pad / pitch) the plan needs.
@@ -66,24 +72,24 @@ void march_plane_geometry(const Canon &c, const MarchLaunch &m, Plane *a, Plane 
 
 struct GenericArgs;
 // pack both planes (for the kernels beside the marching kernel that read planes: border ring, refine, smoothFactor passes)
-hipError_t launch_pack(const Canon &c, const uint8_t *src_a, int stride_a, Plane dst_a, const uint8_t *src_b, int stride_b,
-                       Plane dst_b, hipStream_t s);
-// The hot kernel, on the caller's CV_8UC3 rows themselves (no planes, no pre-pass): img_a carries the outputs (left view:
-// the left image), img_b the candidates.  border: also write the zeros of the out_w x out_h map outside the marching
-// interior (left view).  keys: plane of 8-byte keys (wa x ha, pitch in elements), only touched when m.passes > 1
-hipError_t launch_march(const Canon &c, const MarchLaunch &m, const uint8_t *img_a, int stride_a, const uint8_t *img_b, int stride_b,
-                        float *out, int16_t *out16, int out_pitch, int border, int out_w, int out_h, void *keys, int keys_pitch,
-                        int32_t *cost_out, int cost_pitch,
-                        hipStream_t s); // cost_out: optional plane of the winners' costs (SSD: without sum a^2); out16: see GenericArgs
-const char *march_kernel_name(const Canon &c, const MarchLaunch &m);
-// The SSD search on the int8 matrix cores (ws_march_mfma.hip): plain bytes, left view, one d-group pass of up to 256
-// candidates, a window it is instantiated for, and a search big enough to fill the chip with its 256-column tiles.
-// march_mfma_plan fills the plan if the search is one of those (march_plan asks it when nothing is tuned by hand).
-bool march_mfma_plan(const Canon &c, int num_cus, MarchLaunch *out);
-const char *march_mfma_kernel_name(const Canon &c);
-hipError_t launch_march_mfma(const Canon &c, const MarchLaunch &m, const uint8_t *img_a, int stride_a, const uint8_t *img_b, int stride_b,
-                             float *out, int16_t *out16, int out_pitch, int border, int out_w, int out_h, hipStream_t s);
-bool march_has_cost(const Canon &c); // is there an instantiation that also writes cost_out?
+hipError_t launch_pack(const Canon &c, const MarchLaunch &m, const uint8_t *src_a, int stride_a, Plane dst_a, const uint8_t *src_b,
+                       int stride_b, Plane dst_b, hipStream_t s);
+// What the hot kernel reads and writes: the caller's CV_8UC3 rows themselves (no planes, no pre-pass) -- img_a carries the
+// outputs (left view: the left image), img_b the candidates -- and the map.
+struct MarchIo {
+    const uint8_t *img_a, *img_b;
+    int stride_a, stride_b; // bytes
+    float *out;
+    int16_t *out16;         // see GenericArgs
+    int out_pitch;
+    int border;             // also write the zeros of the out_w x out_h map outside the marching interior (left view)
+    int out_w, out_h;
+    void *keys;             // plane of 8-byte keys (wa x ha, pitch in elements), only touched when m.passes > 1
+    int keys_pitch;
+    int32_t *cost_out;      // optional plane of the winners' costs (SSD: without sum a^2); needs m.fn_cost
+    int cost_pitch;
+};
+hipError_t launch_march(const Canon &c, const MarchLaunch &m, const MarchIo &io, hipStream_t s);
 
 // Brute-force kernels on the original 8-bit images (original coordinates, literal rules).
 struct GenericArgs {
@@ -106,7 +112,7 @@ hipError_t launch_generic(const GenericArgs &g, hipStream_t s);
 constexpr int kLinearMaxRange = 4096;
 hipError_t launch_linear(const GenericArgs &g, hipStream_t s);
 // Right-view border ring on the packed (mirrored) planes: sliding sums along runs, lanes over d.
-hipError_t launch_ring(const Canon &c, Plane a, Plane b, const GenericArgs &skip, float *out, int out_pitch,
+hipError_t launch_ring(const Canon &c, const MarchLaunch &m, Plane a, Plane b, const GenericArgs &skip, float *out, int out_pitch,
                        int32_t *cost_out, int cost_pitch, hipStream_t s);
 // Sub-pixel refinement (extension): parabola through the integer cost at d-1, d, d+1.
 hipError_t launch_refine(const GenericArgs &g, hipStream_t s);
@@ -118,16 +124,17 @@ int smooth_sel_rows(int rows);
 // smoothFactor in [0,1], left view: g.out holds the smoothFactor-1 result on entry
 // top3: smooth_left_top_bytes(w1, h1, s) of scratch (the row-sum volume at its end only for s outside [0,1])
 // gave_up: host-visible word (device pointer) a band of the raster pass sets when it gave up waiting (the map is then invalid)
-hipError_t launch_smooth_left(const GenericArgs &g, double s, uint32_t *top3, const Canon *canon, Plane pa, Plane pb,
-                              unsigned int *gave_up, hipStream_t st);
+hipError_t launch_smooth_left(const GenericArgs &g, double s, uint32_t *top3, const Canon *canon, const MarchLaunch *plan, Plane pa,
+                              Plane pb, unsigned int *gave_up, hipStream_t st);
 size_t smooth_left_top_bytes(int w, int h, double s);
 // bytes of the bit-plane scratch launch_smooth wants for a w x h map
 size_t smooth_planes_bytes(int w, int h);
-// canon / pa / pb: the right view's canonical search and packed planes when the marching kernel ran
+// canon / plan / pa / pb: the right view's canonical search, its plan and packed planes when the marching kernel ran
 // (g's skip rectangle = its interior) together with the cost plane it and the ring kernel wrote,
 // else canon == nullptr
 hipError_t launch_smooth(const GenericArgs &g, double s, uint8_t *sel, int sel_pitch, unsigned long long *planes,
-                         const Canon *canon, Plane pa, Plane pb, const int32_t *cost, int cost_pitch, hipStream_t st);
+                         const Canon *canon, const MarchLaunch *plan, Plane pa, Plane pb, const int32_t *cost, int cost_pitch,
+                         hipStream_t st);
 // nearest-neighbour perspective warp of a float map; minv maps destination -> source pixels
 hipError_t launch_warp(const float *src, int sw, int sh, int sp, float *dst, int dw, int dh, int dp,
                        const double minv[9], hipStream_t s);

@@ -34,11 +34,8 @@
 // No MFMA in this kernel: its hot loop is a stencil + reduction on bytes, bounded by VALU issue and LDS, see
 // DESIGN.md (the SSD searches whose cross term runs on the matrix cores: ws_march_mfma.hip).  Wave64 throughout;
 // nothing here assumes 32-wide warps.
-#include "ws_march_kernel.h"
+#include "ws_march_plan.h"
 
-#include <string.h>
-
-#include <atomic>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -71,18 +68,33 @@ static int min_chunks(MarchShape s) { return s.x > 8 ? s.x : 8; } // (the flush 
 // a shape with more than 8 columns per thread would keep 4 x-runs with 128 chunks
 static int max_chunks(MarchShape s) { return s.x > 8 ? kMaxT / kMinXRuns : kMaxChunks; }
 
-// Row times a search would take with a thread shape, in units of one row step of the 8 x 8 kernel, on a chip of
-// g_model_cus CUs with one workgroup per CU at a time -- the strip planner's own model (march_plan): the chip works through
-// ceil(workgroups / CUs) rounds of strips, a strip of R rows costs R + (wh - 1) / 2 + 3 row steps.  A row step of the
-// 8 x 4 kernel covers half the hypotheses per workgroup and costs 0.62 of an 8 x 8 one (measured: 1.19 .. 1.29 times the
-// time per hypothesis over windows 5 .. 17 at D = 512, profiles/r03/nd_grid.txt).
-// the chip the thread-shape rule plans for: the first context's device (ws_create), 256 CUs without one (ws_plan)
-// (atomic: every ws_create writes it and every context's planner reads it, from any thread -- ws_batch_search_host runs
-// several contexts at once; all the devices of a node are the same chip, so whichever write wins the value is the same)
-static std::atomic<int> g_model_cus{256};
-void march_set_num_cus(int n) { if (n > 0) g_model_cus.store(n, std::memory_order_relaxed); }
+const MarchKnobs &march_knobs()
+{
+    static const MarchKnobs knobs = [] {
+        MarchKnobs k;
+        auto num = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+        k.nd = num("WS_MARCH_ND", 0);
+        k.halo_off = num("WS_MARCH_HALO", 1) == 0;
+        k.halo_ssd_off = num("WS_MARCH_HALO_SSD", 1) == 0;
+        k.slots = num("WS_PLAN_SLOTS", 0);
+        k.threads = num("WS_PLAN_THREADS", 0);
+        const int chunks = num("WS_MAX_CHUNKS", 0);
+        k.max_chunks = chunks >= 8 && chunks <= kMaxT / kMinXRuns ? chunks : 0;
+        k.stage_wave = num("WS_STAGE_WAVE", -1);
+        k.flush_wave = num("WS_FLUSH_WAVE", -1);
+        k.stage_agap = num("WS_STAGE_AGAP", 0);
+        k.mfma = num("WS_MARCH_MFMA", -1);
+        k.stencil_forced = getenv("WS_PLAN_SLOTS") || getenv("WS_PLAN_THREADS") || getenv("WS_MAX_CHUNKS") || getenv("WS_MARCH_ND");
+        return k;
+    }();
+    return knobs;
+}
 
-static double march_model_cost(const Canon &c, MarchShape sh)
+// Row times a search would take with a thread shape, in units of one row step of the 8 x 8 kernel, on a chip of
+// num_cus CUs with one workgroup per CU at a time -- the strip planner's own model (best_strips, ws_march_plan.h).  A row
+// step of the 8 x 4 kernel covers half the hypotheses per workgroup and costs 0.62 of an 8 x 8 one (measured: 1.19 .. 1.29
+// times the time per hypothesis over windows 5 .. 17 at D = 512, profiles/r03/nd_grid.txt).
+static double march_model_cost(const Canon &c, MarchShape sh, int num_cus)
 {
     const int dcount = c.d_hi - c.d_lo + 1, out_w = c.ox1 - c.ox0, out_h = c.oy1 - c.oy0;
     const int nch_total = ceil_div(dcount, sh.nd), passes = ceil_div(nch_total, max_chunks(sh));
@@ -93,26 +105,9 @@ static double march_model_cost(const Canon &c, MarchShape sh)
     if (nxr > need) nxr = need;
     if (nxr < kMinXRuns) nxr = kMinXRuns;
     const int tiles = ceil_div(out_w, nxr * sh.x);
-    double best = 0.0;
-    for (int sc = 1; sc <= out_h; ++sc) {
-        const int rows = ceil_div(out_h, sc), st = ceil_div(out_h, rows);
-        if (st != sc) continue;
-        const double cost = ceil_div(tiles * st, g_model_cus.load(std::memory_order_relaxed)) * (rows + 0.5 * (c.wh - 1) + 3.0);
-        if (sc == 1 || cost < best) best = cost;
-    }
-    return best * passes * (same_shape(sh, kShapeNarrow) ? 0.62 : 1.0);
+    return best_strips(kStencilStrips, out_h, tiles, c.wh, num_cus).cost * passes * (same_shape(sh, kShapeNarrow) ? 0.62 : 1.0);
 }
 
-// Columns x disparities per thread for this search: a function of the canonical problem alone (not of the device), so
-// that everything that reads the marching kernel's planes afterwards (smoothFactor, sub-pixel refine) derives the same
-// key layout.  Round 2 chose from a hand-made table of thresholds taken at one image size.  Now: whichever
-// instantiation the planner's own cost model gives fewer row times.  The 8 x 8 kernel does a hypothesis with ~20 %
-// fewer instructions than the 8 x 4 one (shorter target-image runs per hypothesis) and wins wherever both fill the chip
-// alike; 8 x 4 makes tiles half as wide for the same disparity range, which pays when the range is narrow (D <= ~128 at
-// 1500 columns: the 8 x 8 tiles are then so wide that strips get short and the window's warm-up rows dear) or the image
-// small.  Checked against profiles/r03/nd_grid.txt (1500 x 1000, windows 5 .. 17,
-// D = 128 / 256 / 512, both costs, either instantiation forced) and at 900 x 750 and 2964 x 1988
-// (profiles/r03/nd_rule_check.txt).
 // Does an SSD window's key -- (sum b^2 - 2 sum a.b) << log2(nd), i.e. the SSD minus the reference window's sum of
 // squares -- stay inside (-2^28, 2^28) with nd tags per thread?  Per channel b^2 - 2ab = (b - a)^2 - a^2 lies in
 // [-255^2, 255^2] for plain bytes (bounded by 2 * 255^2 here, as ssd_needs_centring does) and in
@@ -125,41 +120,32 @@ static bool ssd_key_fits(int ww, int wh, int nd)
     return per * ww * wh * 3 * nd < (long long)kValidKeyBound;
 }
 
-static MarchShape march_shape(const Canon &c)
+// Columns x disparities per thread for this search on a chip of num_cus CUs, asked once per plan (the plan carries what
+// follows from it: the kernel, and the key layout of the planes -- `centred` -- for everything that reads them
+// afterwards).  Round 2 chose from a hand-made table of thresholds taken at one image size.  Now: whichever
+// instantiation the planner's own cost model gives fewer row times.  The 8 x 8 kernel does a hypothesis with ~20 %
+// fewer instructions than the 8 x 4 one (shorter target-image runs per hypothesis) and wins wherever both fill the chip
+// alike; 8 x 4 makes tiles half as wide for the same disparity range, which pays when the range is narrow (D <= ~128 at
+// 1500 columns: the 8 x 8 tiles are then so wide that strips get short and the window's warm-up rows dear) or the image
+// small.  Checked against profiles/r03/nd_grid.txt (1500 x 1000, windows 5 .. 17,
+// D = 128 / 256 / 512, both costs, either instantiation forced) and at 900 x 750 and 2964 x 1988
+// (profiles/r03/nd_rule_check.txt).
+static MarchShape march_shape(const Canon &c, int num_cus)
 {
-    static const MarchShape forced = [] {
-        const char *e = getenv("WS_MARCH_ND"); // development knob: 8 or 4
-        MarchShape f{0, 0};
-        if (e && atoi(e) == kND) f = kShapeWide;
-        else if (e && atoi(e) == kNDNarrow) f = kShapeNarrow;
-        return f;
-    }();
-    if (forced.x) return forced;
+    const int forced = march_knobs().nd;
+    if (forced == kND) return kShapeWide;
+    if (forced == kNDNarrow) return kShapeNarrow;
     if (kND == kNDNarrow) return kShapeWide;
     if (c.ox1 <= c.ox0 || c.oy1 <= c.oy0 || c.d_hi < c.d_lo) return kShapeWide;
-    // (asked a dozen times per search -- by the planner, the launchers, everything that needs the key layout -- and the
-    // model walks every strip count: remembered per thread for the last few problems, or a 30 us search would spend
-    // 50 us of host time on it)
-    struct Memo { int key[9]; MarchShape shape; };
-    thread_local Memo memo[4] = {};
-    thread_local int next = 0;
-    const int key[9] = {c.ox1 - c.ox0, c.oy1 - c.oy0, c.d_hi - c.d_lo + 1, c.ww, c.wh, c.ssd, 1, g_model_cus.load(std::memory_order_relaxed), 0};
-    for (const Memo &m : memo)
-        if (!memcmp(m.key, key, sizeof key)) return m.shape;
-    MarchShape sh = march_model_cost(c, kShapeNarrow) < march_model_cost(c, kShapeWide) ? kShapeNarrow : kShapeWide;
+    MarchShape sh = march_model_cost(c, kShapeNarrow, num_cus) < march_model_cost(c, kShapeWide, num_cus) ? kShapeNarrow : kShapeWide;
     // (centred SSD windows of 16 x 16 and more: a maximum-contrast window's key needs the narrower shape's 2 tag bits)
     if (c.ssd && same_shape(sh, kShapeWide) && !ssd_key_fits(c.ww, c.wh, kShapeWide.nd) && ssd_key_fits(c.ww, c.wh, kShapeNarrow.nd))
         sh = kShapeNarrow;
-    memcpy(memo[next].key, key, sizeof key);
-    memo[next].shape = sh;
-    next = (next + 1) & 3;
     return sh;
 }
-static int march_nd(const Canon &c) { return march_shape(c).nd; }
 
-static const MarchEntry *find_march(const Canon &c)
+static const MarchEntry *find_march(const Canon &c, MarchShape sh)
 {
-    const MarchShape sh = march_shape(c);
     int n = (int)(sizeof kMarchWide / sizeof kMarchWide[0]);
     const MarchEntry *t = kMarchWide;
     if (same_shape(sh, kShapeNarrow)) t = march_table_narrow(&n);
@@ -169,17 +155,10 @@ static const MarchEntry *find_march(const Canon &c)
 }
 
 // the halo-exchange twin of the packed SAD kernel for this window, if there is one (and the wide shape was chosen)
-static const MarchEntry *find_march_halo(const Canon &c)
+static const MarchEntry *find_march_halo(const Canon &c, MarchShape sh)
 {
-    static const bool off = [] {
-        const char *e = getenv("WS_MARCH_HALO"); // development knob: 0 = never
-        return e && atoi(e) == 0;
-    }();
-    static const bool ssd_off = [] {
-        const char *e = getenv("WS_MARCH_HALO_SSD"); // development knob: 0 = not for SSD
-        return e && atoi(e) == 0;
-    }();
-    if (off || (c.ssd && ssd_off) || !same_shape(march_shape(c), kShapeWide)) return nullptr;
+    const MarchKnobs &k = march_knobs();
+    if (k.halo_off || (c.ssd && k.halo_ssd_off) || !same_shape(sh, kShapeWide)) return nullptr;
     for (const MarchEntry &e : kMarchHalo)
         if (e.ww == c.ww && e.wh == c.wh && e.ssd == c.ssd) return &e;
     return nullptr;
@@ -192,38 +171,32 @@ static int tag_bits_for(const Canon &c)
     return bits;
 }
 
-bool march_has_cost(const Canon &c)
-{
-    const MarchEntry *e = find_march(c);
-    return e && e->fn_cost;
-}
+// What march_plan decides before any tiling: the thread shape and the table entries that go with it.
+struct MarchChoice {
+    MarchShape shape;
+    const MarchEntry *plain, *halo; // the window's instantiation with that shape; its halo-exchange twin or null
+};
 
-int march_centred(const Canon &c) { return c.ssd && ssd_needs_centring(c.ww, c.wh, march_nd(c)); }
-
-bool march_supported(const Canon &c)
+static bool march_supported(const Canon &c, const MarchChoice &ch)
 {
-    if (!find_march(c)) return false;
+    if (!ch.plain) return false;
     if (c.ox1 <= c.ox0 || c.oy1 <= c.oy0) return false;
     const int dcount = c.d_hi - c.d_lo + 1;
     if (dcount < 1) return false;
     // keys must stay inside (-2^28, 2^28)
     //   SSD: (sum b^2 - 2 cross sum) << tie-tag bits (ssd_key_fits)     SAD: window sum << tag bits
     if (!c.ssd && march_pk_window(c.ww, c.wh)) return dcount <= 65536; // packed SAD: 16-bit cost, 16-bit global tie tag
-    if (c.ssd) return ssd_key_fits(c.ww, c.wh, march_nd(c));
+    if (c.ssd) return ssd_key_fits(c.ww, c.wh, ch.shape.nd);
     return (((long long)c.ww * c.wh * 3 * 255) << tag_bits_for(c)) < (long long)kValidKeyBound;
 }
 
-static int march_slots_per_cu(const Canon &c, int nd, int threads, bool halo)
+static int march_slots_per_cu(const Canon &c, const MarchChoice &ch, int threads, bool halo)
 {
-    static const int forced = [] {
-        const char *e = getenv("WS_PLAN_SLOTS"); // development knob
-        return e ? atoi(e) : 0;
-    }();
-    if (forced > 0) return forced;
-    const MarchEntry *e = halo ? find_march_halo(c) : find_march(c);
+    if (march_knobs().slots > 0) return march_knobs().slots;
+    const MarchEntry *e = halo ? ch.halo : ch.plain;
     // (without a device: the 8 x 4 kernels of packed SAD up to 6 x 6 and of SSD up to 3 x 3 stay within 128 VGPRs)
     // every instantiation runs two waves per SIMD at least: two workgroups of 256 threads share a CU
-    const int guess = threads <= 256 || (same_shape(march_shape(c), kShapeNarrow) && threads <= 512 && (c.ssd ? c.ww <= 3 : c.ww <= 6)) ? 2 : 1;
+    const int guess = threads <= 256 || (same_shape(ch.shape, kShapeNarrow) && threads <= 512 && (c.ssd ? c.ww <= 3 : c.ww <= 6)) ? 2 : 1;
     if (!e) return guess;
     // one question per kernel and block size, asked once (LDS never is the limit at these sizes)
     static std::mutex mu;
@@ -242,7 +215,8 @@ static int march_slots_per_cu(const Canon &c, int nd, int threads, bool halo)
     return slots;
 }
 
-static bool march_plan_threads(const Canon &c, int num_cus, int tune_nxr, int tune_strip_rows, int tune_threads, MarchLaunch *out);
+static bool march_plan_threads(const Canon &c, const MarchChoice &ch, int num_cus, int tune_nxr, int tune_strip_rows, int tune_threads,
+                               MarchLaunch *out);
 
 // Workgroups of 512 threads (two waves per SIMD, one workgroup per CU) or of 256 (one wave per SIMD each, two
 // workgroups per CU with barriers of their own: while one waits for its slowest wave the other one's wave has the
@@ -255,12 +229,12 @@ static bool march_plan_threads(const Canon &c, int num_cus, int tune_nxr, int tu
 bool march_plan(const Canon &c, int num_cus, int tune_nxr, int tune_strip_rows, int tune_threads,
                 MarchLaunch *out)
 {
-    static const int env_threads = [] {
-        const char *e = getenv("WS_PLAN_THREADS"); // development knob
-        return e ? atoi(e) : 0;
-    }();
-    if (tune_threads <= 0 && env_threads >= 64) tune_threads = env_threads;
-    if (!march_plan_threads(c, num_cus, tune_nxr, tune_strip_rows, tune_threads, out)) return false;
+    if (tune_threads <= 0 && march_knobs().threads >= 64) tune_threads = march_knobs().threads;
+    MarchChoice ch{};
+    ch.shape = march_shape(c, num_cus);
+    ch.plain = find_march(c, ch.shape);
+    ch.halo = find_march_halo(c, ch.shape);
+    if (!march_plan_threads(c, ch, num_cus, tune_nxr, tune_strip_rows, tune_threads, out)) return false;
     if (tune_threads > 0 || tune_nxr > 0 || tune_strip_rows > 0) return true; // (a forced tuning means the stencil kernel)
     if (march_mfma_plan(c, num_cus, out)) return true;
     MarchLaunch half{};
@@ -269,31 +243,30 @@ bool march_plan(const Canon &c, int num_cus, int tune_nxr, int tune_strip_rows, 
     // Mdisp/s with two searches in flight, 3.85 -> 3.52 alone -- gpurun_out/r3_halo.txt)
     const int launches = out->halo ? out->passes : 1;
     if (out->threads == kMaxT && 2 * out->tiles * out->strips * launches >= 3 * num_cus &&
-        march_plan_threads(c, num_cus, 0, 0, kMaxT / 2, &half) && (half.passes == out->passes || (half.halo && out->halo)))
+        march_plan_threads(c, ch, num_cus, 0, 0, kMaxT / 2, &half) && (half.passes == out->passes || (half.halo && out->halo)))
         *out = half;
     return true;
 }
 
-static bool march_plan_threads(const Canon &c, int num_cus, int tune_nxr, int tune_strip_rows, int tune_threads, MarchLaunch *out)
+static bool march_plan_threads(const Canon &c, const MarchChoice &ch, int num_cus, int tune_nxr, int tune_strip_rows, int tune_threads,
+                               MarchLaunch *out)
 {
-    if (!march_supported(c)) return false;
+    if (!march_supported(c, ch)) return false;
     MarchLaunch m{};
-    const MarchShape sh = march_shape(c);
+    const MarchShape sh = ch.shape;
     const int nd = sh.nd, X = sh.x;
     m.x_per_thread = X;
     m.nd_per_thread = nd;
     m.max_threads = kMaxT;
+    m.centred = c.ssd && ssd_needs_centring(c.ww, c.wh, nd);
+    m.tag_bits = tag_bits_for(c);
     const int dcount = c.d_hi - c.d_lo + 1;
     const int out_w = c.ox1 - c.ox0, out_h = c.oy1 - c.oy0;
     // d-chunks per tile.  One tile holds at most kMaxChunks chunks (wider disparity ranges would
     // leave too few columns per tile); beyond that the range is cut into equal d-group passes that
     // meet in a plane of keys.
     const int nch_total = ceil_div(dcount, nd);
-    static const int forced_chunks = [] {
-        const char *e = getenv("WS_MAX_CHUNKS"); // development knob
-        const int v = e ? atoi(e) : 0;
-        return v >= 8 && v <= kMaxT / kMinXRuns ? v : 0;
-    }();
+    const int forced_chunks = march_knobs().max_chunks;
     int maxt = kMaxT;
     if (tune_threads >= 64 && tune_threads < kMaxT) maxt = tune_threads / 64 * 64;
     m.passes = ceil_div(nch_total, forced_chunks ? forced_chunks : max_chunks(sh));
@@ -313,33 +286,18 @@ static bool march_plan_threads(const Canon &c, int num_cus, int tune_nxr, int tu
         const int tx = runs * X;
         p.tile_cols = p.halo ? tx - X : tx;
         p.tiles = ceil_div(out_w, p.tile_cols);
-        // One workgroup per CU at a time (its registers fill the CU).  A strip of R rows costs about
-        // R + (wh - 1) / 2 + 3 row times (the wh - 1 warm-up rows only add, the prologue is worth ~3 rows) and the
-        // chip works through ceil(workgroups / CUs) rounds of them: take the strip count with the cheapest total
-        // (config 3's own sweep, profiles/r01/sweep_tiles_config3.csv, has its minimum where this puts it).
-        // (With 4 disparities per thread and a window up to 9 x 9 the kernel stays within 128 VGPRs: two
-        // workgroups share a CU, four waves per SIMD, and a round is twice as many workgroups -- the runtime's
-        // occupancy figure where a device is there to ask, that rule of thumb for ws_plan without one.)
         const int pnd = p.nd_per_thread;
         p.lds_bytes = (size_t)march_lds_layout(X, pnd, c.ww, c.wh, c.ssd != 0, p.halo && !c.ssd && march_pk_window(c.ww, c.wh), runs, p.nch).bytes;
         if (p.lds_bytes == 0 || p.lds_bytes > 160 * 1024) return 0.0; // (0: a tile row wider than the kernel's stage area)
+        // One workgroup per CU at a time (its registers fill the CU); take the strip count the strip model gives the
+        // cheapest total.  (With 4 disparities per thread and a window up to 9 x 9 the kernel stays within 128 VGPRs:
+        // two workgroups share a CU, four waves per SIMD, and a round is twice as many workgroups -- the runtime's
+        // occupancy figure where a device is there to ask, that rule of thumb for ws_plan without one.)
         // (the registers' answer, capped by what the CU's 160 KB of LDS hold: the kernel's LDS is dynamic, the runtime is
         // asked without it -- and since round 4 a workgroup's LDS carries the stage area and the descriptors as well)
-        const int slots = std::max(1, std::min(march_slots_per_cu(c, pnd, p.threads, p.halo != 0), (int)(160 * 1024 / p.lds_bytes)));
-        auto strip_cost = [&](int st, int rows) { return ceil_div(p.tiles * st, num_cus * slots) * (rows + 0.5 * (c.wh - 1) + 3.0); };
-        int strips = 1;
-        if (tune_strip_rows > 0) {
-            strips = ceil_div(out_h, tune_strip_rows);
-        } else {
-            double best_cost = 0.0;
-            for (int sc = 1; sc <= out_h; ++sc) {
-                const int rows = ceil_div(out_h, sc), st = ceil_div(out_h, rows);
-                if (st != sc) continue; // (the same strips as a smaller count already seen)
-                const double cost = strip_cost(st, rows);
-                if (sc == 1 || cost < best_cost) { best_cost = cost; strips = sc; }
-            }
-            if (strips > out_h) strips = out_h;
-        }
+        const int slots = std::max(1, std::min(march_slots_per_cu(c, ch, p.threads, p.halo != 0), (int)(160 * 1024 / p.lds_bytes)));
+        const int strips = tune_strip_rows > 0 ? ceil_div(out_h, tune_strip_rows)
+                                               : best_strips(kStencilStrips, out_h, p.tiles, c.wh, num_cus * slots).strips;
         p.strip_rows = ceil_div(out_h, strips);
         p.strips = ceil_div(out_h, p.strip_rows);
         // a row step of the halo-exchange kernel against the plain one's, from the instruction counts (march_pk_halo);
@@ -350,10 +308,12 @@ static bool march_plan_threads(const Canon &c, int num_cus, int tune_nxr, int tu
                             : c.ssd ? (c.ww >= 8 ? 0.87 : 0.93) * pnd / nd // (measured: config 5, 9 x 9: -6.7 %; config 2, 7 x 7: 50 instead of 56
                                                                            // instructions per disparity and step, 0.1205 vs 0.1208 ms with 59- instead of 54-row strips)
                                     : (c.ww >= 9 ? 0.82 : c.ww == 8 ? 0.83 : c.ww == 7 ? 0.85 : 0.87) * pnd / nd;
-        return p.passes * (1.0 + 0.02 * (p.passes - 1)) * step * strip_cost(p.strips, p.strip_rows);
+        return p.passes * (1.0 + 0.02 * (p.passes - 1)) * step * strip_cost(kStencilStrips, p.tiles, p.strips, p.strip_rows, c.wh, num_cus * slots);
     };
+    auto names = [](MarchLaunch &p, const MarchEntry *e) { p.fn = e->fn; p.fn_cost = e->fn_cost; p.name = e->name; };
     m.halo = 0;
     MarchLaunch best = m;
+    names(best, ch.plain);
     const double plain_cost = complete(best, nxr);
     // Packed SAD with the halo exchange: the last run of a tile only feeds its neighbour, so tiles want MANY runs --
     // 16 (a row of DPP lanes; 1/16 of the threads lost) or 8, rather than the 4 .. 8 a wide disparity range leaves
@@ -363,7 +323,7 @@ static bool march_plan_threads(const Canon &c, int num_cus, int tune_nxr, int tu
     // other width the plain one)
     double best_cost = plain_cost;
     const bool tuned_halo = tune_nxr == 16 || tune_nxr == 8;
-    if (find_march_halo(c) && (tune_nxr <= 0 || tuned_halo) && !forced_chunks) {
+    if (ch.halo && (tune_nxr <= 0 || tuned_halo) && !forced_chunks) {
         if (tuned_halo) best_cost = 0.0;
         for (int hx : {16, 8}) { // (powers of two: lane + 1 is the next run inside a DPP row)
             if (tuned_halo && hx != tune_nxr) continue;
@@ -372,7 +332,8 @@ static bool march_plan_threads(const Canon &c, int num_cus, int tune_nxr, int tu
             if (hch < min_chunks(sh)) continue;
             MarchLaunch h = m;
             h.halo = 1;
-            const int hnd = find_march_halo(c)->nd; // 16 for the packed SAD kernels, 8 for the SSD ones
+            names(h, ch.halo);
+            const int hnd = ch.halo->nd; // 16 for the packed SAD kernels, 8 for the SSD ones
             h.nd_per_thread = hnd;
             const int hch_total = ceil_div(dcount, hnd);
             h.passes = ceil_div(hch_total, hch);
@@ -416,66 +377,14 @@ void march_plane_geometry(const Canon &c, const MarchLaunch &m, Plane *a, Plane 
     b->pitch = round_up(std::max(base_b + last + round_up(n_b, 4), c.wb) + b->pad + 4, 64);
 }
 
-
-const char *march_kernel_name(const Canon &c, const MarchLaunch &m)
-{
-    if (m.mfma) return march_mfma_kernel_name(c);
-    const MarchEntry *e = m.halo ? find_march_halo(c) : find_march(c);
-    return e ? e->name : "";
-}
-
-hipError_t launch_march(const Canon &c, const MarchLaunch &m, const uint8_t *img_a, int stride_a, const uint8_t *img_b, int stride_b,
-                        float *out, int16_t *out16, int out_pitch, int border, int out_w, int out_h, void *keys, int keys_pitch,
-                        int32_t *cost_out, int cost_pitch, hipStream_t s)
+hipError_t launch_march(const Canon &c, const MarchLaunch &m, const MarchIo &io, hipStream_t s)
 {
     if (m.mfma) {
-        if (cost_out || m.passes != 1) return hipErrorInvalidValue;
-        return launch_march_mfma(c, m, img_a, stride_a, img_b, stride_b, out, out16, out_pitch, border, out_w, out_h, s);
+        if (io.cost_out || m.passes != 1) return hipErrorInvalidValue;
+        return launch_march_mfma(c, m, io, s);
     }
-    const MarchEntry *e = m.halo ? find_march_halo(c) : find_march(c);
-    if (!e) return hipErrorInvalidValue;
-    MarchArgs g{};
-    g.st.img_a = img_a;
-    g.st.stride_a = stride_a;
-    g.st.img_b = img_b;
-    g.st.stride_b = stride_b;
-    g.st.wb = c.wb;
-    g.out = out;
-    g.out16 = out16;
-    g.out_pitch = out_pitch;
-    g.border = border;
-    g.out_w = out_w;
-    g.out_h = out_h;
-    g.st.wa = c.wa;
-    g.st.nxr = m.nxr;
-    g.st.nch = m.nch;
-    g.st.wx0 = c.wx0;
-    g.wy0 = c.wy0;
-    g.st.boff = c.boff;
-    g.d_lo = c.d_lo;
-    g.d_hi = c.d_hi;
-    g.d_top = c.d_lo + m.passes * m.nch * m.nd_per_thread - 1;
-    g.st.b_lo = c.b_lo;
-    g.st.b_hi = c.b_hi;
-    g.tag_bits = tag_bits_for(c);
-    g.ox0 = c.ox0;
-    g.ox1 = c.ox1;
-    g.oy0 = c.oy0;
-    g.oy1 = c.oy1;
-    g.strip_rows = m.strip_rows;
-    g.tiles = m.tiles;
-    g.tile_stride = m.tile_cols;
-    g.strips = m.strips;
-    g.prefer_large = c.prefer_large;
-    g.st.mirror = c.mirror;
-    g.fallback_neg = c.fallback_neg;
-    static const int env_prod = [] { const char *v = getenv("WS_STAGE_WAVE"); return v ? atoi(v) : -1; }();  // development knobs
-    static const int env_flush = [] { const char *v = getenv("WS_FLUSH_WAVE"); return v ? atoi(v) : -1; }();
-    g.tune_prod_wave = env_prod;
-    g.tune_flush_wave = env_flush;
-    static const int env_agap = [] { const char *v = getenv("WS_STAGE_AGAP"); return v ? atoi(v) : 0; }();
-    g.tune_a_gap = env_agap;
-    const MarchFn fn = cost_out ? e->fn_cost : e->fn;
+    MarchArgs g = march_args(c, m, io);
+    const MarchFn fn = io.cost_out ? m.fn_cost : m.fn;
     if (!fn) return hipErrorInvalidValue;
     if (m.lds_bytes > 48 * 1024) {
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
@@ -484,10 +393,6 @@ hipError_t launch_march(const Canon &c, const MarchLaunch &m, const uint8_t *img
         if (err != hipSuccess) return err;
     }
     dim3 grid(round_up(m.tiles * m.strips, 8));
-    g.keys = keys;
-    g.keys_pitch = keys_pitch;
-    g.cost_out = cost_out;
-    g.cost_pitch = cost_pitch;
     for (int pass = 0; pass < m.passes; ++pass) {
         g.st.d_first = c.d_lo + pass * m.nch * m.nd_per_thread;
         g.pass_mode = m.passes == 1 ? 0 : pass == 0 ? 1 : pass == m.passes - 1 ? 3 : 2;

@@ -1279,8 +1279,7 @@ __global__ void __launch_bounds__(MAXT) ws_march_kernel(const MarchArgs g)
     flush(nsteps - (WH - 1)); // the last row
 }
 
-typedef void (*MarchFn)(const MarchArgs);
-struct MarchEntry {
+struct MarchEntry { // (MarchFn: ws_kernels.h)
     int x, ww, wh, ssd, nd; // columns x disparities per thread, window, cost
     MarchFn fn;
     MarchFn fn_cost; // the same kernel also writing the winners' costs (right-view window sizes only)

@@ -76,12 +76,11 @@ __global__ void __launch_bounds__(256) ws_pack_kernel(const PackLaunchArgs g)
     pack_block(g.pack, 1, b % g.pack_gx[1], b / g.pack_gx[1]);
 }
 
-hipError_t launch_pack(const Canon &c, const uint8_t *src_a, int stride_a, Plane dst_a, const uint8_t *src_b, int stride_b,
-                       Plane dst_b, hipStream_t s)
+hipError_t launch_pack(const Canon &c, const MarchLaunch &m, const uint8_t *src_a, int stride_a, Plane dst_a, const uint8_t *src_b,
+                       int stride_b, Plane dst_b, hipStream_t s)
 {
     PackLaunchArgs g{};
-    const int centred = march_centred(c);
-    g.pack.xor_mask = centred ? kCentre : 0u;
+    g.pack.xor_mask = m.centred ? kCentre : 0u;
     g.pack.src[0] = src_a; g.pack.dst[0] = dst_a.data; g.pack.w[0] = c.wa; g.pack.h[0] = c.ha; g.pack.stride[0] = stride_a;
     g.pack.pitch[0] = dst_a.pitch; g.pack.pad[0] = dst_a.pad;
     g.pack.src[1] = src_b; g.pack.dst[1] = dst_b.data; g.pack.w[1] = c.wb; g.pack.h[1] = c.hb; g.pack.stride[1] = stride_b;

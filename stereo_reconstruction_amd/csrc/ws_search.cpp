@@ -13,8 +13,9 @@ namespace {
 
 // What a canonical search leaves for the passes after it (smoothFactor).
 struct SearchResult {
-    bool planes = false; // the marching kernel ran and packed the dword planes (canon, pa and pb are read only then)
+    bool planes = false; // the marching kernel ran and packed the dword planes (canon, plan, pa and pb are read only then)
     Canon canon{};
+    MarchLaunch plan{};
     Plane pa{}, pb{};
     int32_t *cost = nullptr;           // the winners' costs (pitch canon.wa), or null
     const int32_t *bs_plane = nullptr; // varBlock: the windows ws_varblock_kernel chose (pitch (R->width + 63) & ~63)
@@ -77,16 +78,10 @@ int run_canonical(Searcher &S, std::string *err, const ws_params *p, const ws_im
     Canon c{};
     MarchLaunch m{};
     bool march = make_canon(p, L, R, &c);
-    if (march && !(S.plan_valid && !memcmp(&S.plan_canon, &c, sizeof c) && !memcmp(S.plan_tune, S.tune, sizeof S.tune))) {
-        S.plan_launch = MarchLaunch{};
-        S.plan_ok = march_plan(c, S.num_cus, S.tune[0], S.tune[1], S.tune[2], &S.plan_launch);
-        S.plan_canon = c;
-        memcpy(S.plan_tune, S.tune, sizeof S.tune);
-        S.plan_valid = true;
-    }
     if (march) {
-        m = S.plan_launch;
-        march = S.plan_ok;
+        const Searcher::CachedPlan &plan = S.plan_for(c);
+        m = plan.launch;
+        march = plan.ok;
     }
     // Dword planes of both images: only for the kernels BESIDE the marching kernel that still read them -- the right
     // view's border ring, the sub-pixel refine, the smoothFactor passes.  The marching kernel reads the caller's bytes.
@@ -103,24 +98,29 @@ int run_canonical(Searcher &S, std::string *err, const ws_params *p, const ws_im
             if ((rc = ensure(err, S.plane_b, (size_t)pb.pitch * c.hb * 4)) != WS_OK) return rc;
             pa.data = static_cast<uint32_t *>(S.plane_a.p);
             pb.data = static_cast<uint32_t *>(S.plane_b.p);
-            WS_HIP(err, launch_pack(c, ia->data, ia->stride, pa, ib->data, ib->stride, pb, s));
+            WS_HIP(err, launch_pack(c, m, ia->data, ia->stride, pa, ib->data, ib->stride, pb, s));
         }
         if (S.profiling) WS_HIP(err, hipEventRecord(S.evk0, s));
         const int keys_pitch = (c.wa + 15) & ~15;
         if (m.passes > 1 && (rc = ensure(err, S.keys, (size_t)keys_pitch * c.ha * 8)) != WS_OK) return rc;
-        if (keep_cost && march_has_cost(c)) {
+        if (keep_cost && m.fn_cost) {
             if ((rc = ensure(err, S.cost, (size_t)c.wa * c.ha * 4)) != WS_OK) return rc;
             res->cost = static_cast<int32_t *>(S.cost.p);
         }
         // left view: the marching kernel also writes the zeros outside its interior (BlockSearch.cpp:33,36,38); the
         // right view's ring runs on the packed planes after it
-        WS_HIP(err, launch_march(c, m, ia->data, ia->stride, ib->data, ib->stride, out, out16, out_stride,
-                                 p->view == WS_VIEW_LEFT, L->width, L->height, S.keys.p, keys_pitch, res->cost, c.wa, s));
+        MarchIo io{};
+        io.img_a = ia->data; io.stride_a = ia->stride; io.img_b = ib->data; io.stride_b = ib->stride;
+        io.out = out; io.out16 = out16; io.out_pitch = out_stride;
+        io.border = p->view == WS_VIEW_LEFT; io.out_w = L->width; io.out_h = L->height;
+        io.keys = S.keys.p; io.keys_pitch = keys_pitch;
+        io.cost_out = res->cost; io.cost_pitch = c.wa;
+        WS_HIP(err, launch_march(c, m, io, s));
         if (S.profiling) {
             WS_HIP(err, hipEventRecord(S.evk1, s));
             S.kernel_timed = true;
         }
-        S.launched(march_kernel_name(c, m), m.threads, m.tiles * m.strips, (int)m.lds_bytes);
+        S.launched(m.name, m.threads, m.tiles * m.strips, (int)m.lds_bytes);
     } else {
         // (launch_linear hands ranges beyond kLinearMaxRange to the brute-force kernel: name the one that runs)
         S.launched(p->view == WS_VIEW_LINEAR && p->linear_range <= kLinearMaxRange ? "ws_linear_kernel" : "ws_generic_kernel", 256,
@@ -128,13 +128,14 @@ int run_canonical(Searcher &S, std::string *err, const ws_params *p, const ws_im
     }
     // everything the marching kernel does not own: border ring, rows past min(h1,h2), or all of it
     if (march && p->view == WS_VIEW_RIGHT)
-        WS_HIP(err, launch_ring(c, res->pa, res->pb, ga, out, out_stride, res->cost, c.wa, s));
+        WS_HIP(err, launch_ring(c, m, res->pa, res->pb, ga, out, out_stride, res->cost, c.wa, s));
     else if (!march && p->view == WS_VIEW_LINEAR)
         WS_HIP(err, launch_linear(ga, s));
     else if (!march)
         WS_HIP(err, launch_generic(ga, s));
     res->planes = planes;
     res->canon = c;
+    res->plan = m;
     if (p->subpixel) {
         if (march) WS_HIP(err, launch_refine_planes(c, m, res->pa, res->pb, out, out_stride, s));
         WS_HIP(err, launch_refine(ga, s)); // the pixels outside the marching interior (all of them without it)
@@ -163,7 +164,7 @@ int search_on(Searcher &S, std::string *err, const ws_params *p, const ws_image 
         // per pixel the best candidate's cost (0 <= s <= 1) or the three best candidates
         if ((rc = ensure(err, S.top3, smooth_left_top_bytes(L->width, L->height, p->smooth_factor))) != WS_OK) return rc;
         WS_HIP(err, launch_smooth_left(ga, p->smooth_factor, static_cast<uint32_t *>(S.top3.p), r.planes ? &r.canon : nullptr,
-                                       r.pa, r.pb, status, s));
+                                       &r.plan, r.pa, r.pb, status, s));
         return WS_OK;
     }
     q.min_disparity = 1; // the data-parallel part: best candidate among d >= 1
@@ -181,12 +182,26 @@ int search_on(Searcher &S, std::string *err, const ws_params *p, const ws_image 
     const bool on_planes = r.planes && r.cost;
     if (on_planes) skip_interior(r.canon, &ga);
     WS_HIP(err, launch_smooth(ga, p->smooth_factor, static_cast<uint8_t *>(S.sel.p), sel_pitch,
-                              static_cast<unsigned long long *>(S.sel_planes.p), on_planes ? &r.canon : nullptr, r.pa, r.pb,
+                              static_cast<unsigned long long *>(S.sel_planes.p), on_planes ? &r.canon : nullptr, &r.plan, r.pa, r.pb,
                               on_planes ? r.cost : nullptr, on_planes ? r.canon.wa : 0, s));
     return WS_OK;
 }
 
 } // namespace
+
+const Searcher::CachedPlan &Searcher::plan_for(const Canon &c)
+{
+    for (const CachedPlan &e : plans)
+        if (e.valid && !memcmp(&e.canon, &c, sizeof c) && !memcmp(e.tune, tune, sizeof tune)) return e;
+    CachedPlan &e = plans[plan_next];
+    plan_next = (plan_next + 1) % (int)(sizeof plans / sizeof plans[0]);
+    e.launch = MarchLaunch{};
+    e.ok = march_plan(c, num_cus, tune[0], tune[1], tune[2], &e.launch);
+    e.canon = c;
+    memcpy(e.tune, tune, sizeof tune);
+    e.valid = true;
+    return e;
+}
 
 int check_params(std::string *err, const ws_params *p, const ws_image *L, const ws_image *R)
 {

@@ -11,12 +11,18 @@ namespace wsamd {
 struct Searcher {
     int num_cus = 256; // the device's, for the planner
     DevBuf plane_a, plane_b, keys, cost, bs_plane, max_block, sel, sel_planes, top3;
-    // the last problem's plan: a queue of equal pairs asks for the same one every call, and the planner walks every
-    // strip count for up to three candidate tilings and two workgroup sizes -- 5 us of a 15 us enqueue
-    bool plan_valid = false, plan_ok = false;
-    Canon plan_canon{};
-    int plan_tune[3] = {0, 0, 0};
-    MarchLaunch plan_launch{};
+    // the last few problems' plans, keyed on (Canon, tuning): a queue of equal pairs asks for the same one every call, the
+    // left-right check for two in turn, and the planner walks every strip count for two thread shapes, up to three
+    // candidate tilings and two workgroup sizes -- 5 us of a 15 us enqueue
+    struct CachedPlan {
+        bool valid = false, ok = false; // ok: march_plan's answer (launch holds a plan)
+        Canon canon{};
+        int tune[3] = {0, 0, 0};
+        MarchLaunch launch{};
+    };
+    CachedPlan plans[4];
+    int plan_next = 0; // the entry the next new problem replaces (round robin)
+    const CachedPlan &plan_for(const Canon &c);
     int tune[3] = {0, 0, 0};              // ws_set_tuning: x-runs per tile, strip rows, threads (0 = automatic)
     hipEvent_t ev_scratch = nullptr;      // end of the last search: the scratch planes are free again
     hipStream_t scratch_stream = nullptr; // ... the stream it ran on

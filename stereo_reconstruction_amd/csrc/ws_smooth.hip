@@ -1476,7 +1476,7 @@ size_t smooth_left_top_bytes(int w, int h, double s)
     return (size_t)w * h * kTopWords * sizeof(uint32_t) + smooth_left_sync_bytes(w, h) + (outside ? smooth_left_vol_bytes(w, h) : 0);
 }
 
-hipError_t launch_smooth_left(const GenericArgs &g, double s, uint32_t *top3, const Canon *canon, Plane pa, Plane pb,
+hipError_t launch_smooth_left(const GenericArgs &g, double s, uint32_t *top3, const Canon *canon, const MarchLaunch *plan, Plane pa, Plane pb,
                               unsigned int *gave_up, hipStream_t st)
 {
     SmoothLeftArgs a{};
@@ -1490,7 +1490,7 @@ hipError_t launch_smooth_left(const GenericArgs &g, double s, uint32_t *top3, co
     if (canon) { // the marching kernel ran: its planes are the two images, one dword per pixel
         a.A = pa.data; a.B = pb.data;
         a.pitch_a = pa.pitch; a.pad_a = pa.pad; a.pitch_b = pb.pitch; a.pad_b = pb.pad;
-        a.centred = march_centred(*canon);
+        a.centred = plan->centred;
     }
     a.L = g.L; a.R = g.R; a.w1 = g.w1; a.h1 = g.h1; a.s1 = g.s1; a.w2 = g.w2; a.h2 = g.h2; a.s2 = g.s2;
     a.block_size = g.block_size; a.max_d = g.max_d; a.ssd = g.ssd; a.s = s;
@@ -1841,7 +1841,7 @@ size_t smooth_planes_bytes(int w, int h)
 }
 
 hipError_t launch_smooth(const GenericArgs &g, double s, uint8_t *sel, int sel_pitch, unsigned long long *planes,
-                         const Canon *canon, Plane pa, Plane pb, const int32_t *cost, int cost_pitch, hipStream_t st)
+                         const Canon *canon, const MarchLaunch *plan, Plane pa, Plane pb, const int32_t *cost, int cost_pitch, hipStream_t st)
 {
     if (canon) { // right view after the marching kernel: everything on the packed planes + the cost plane
         PreparePlanesArgs a{};
@@ -1863,7 +1863,7 @@ hipError_t launch_smooth(const GenericArgs &g, double s, uint8_t *sel, int sel_p
         if (!canon->ssd) {
             hipLaunchKernelGGL((ws_smooth_prepare_box_kernel<false, false>), gi, dim3(256), 0, st, a);
             if (nring > 0) hipLaunchKernelGGL((ws_smooth_prepare_ring_kernel<false, false>), gr, dim3(256), 0, st, a);
-        } else if (march_centred(*canon)) {
+        } else if (plan->centred) {
             hipLaunchKernelGGL((ws_smooth_prepare_box_kernel<true, true>), gi, dim3(256), 0, st, a);
             if (nring > 0) hipLaunchKernelGGL((ws_smooth_prepare_ring_kernel<true, true>), gr, dim3(256), 0, st, a);
         } else {
