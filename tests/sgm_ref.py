@@ -49,20 +49,26 @@ def volume(L, R, view, block_size, min_disparity, max_disparity, cost):
     return vol, d0, node, region, blk
 
 
-def _step(Lq, vq, qnode, C, vp, p1, p2):
+def _step(Lq, vq, qnode, C, vp, p1, p2, cut=None):
     """One path step across a line of pixels: Lq, vq, C, vp are [nd, n]; qnode [n].  Returns Lr [nd, n] (BIG where d is
-    not a candidate of p)."""
+    not a candidate of p).  cut (tests/test_sgm_inputs.py only): indices j whose P1 link with j - 1 is left out, in both
+    directions -- a deliberately wrong aggregation that shows which pixels of a map the link decides."""
     lq = np.where(vq, Lq, BIG)
     m = lq.min(axis=0) if lq.shape[0] else np.zeros(lq.shape[1], np.int64)
     best = np.minimum(lq, m[None, :] + p2)
     if lq.shape[0] > 1:
-        best[1:] = np.minimum(best[1:], np.where(vq[:-1], Lq[:-1] + p1, BIG))   # Lr(q, d-1) + P1
-        best[:-1] = np.minimum(best[:-1], np.where(vq[1:], Lq[1:] + p1, BIG))   # Lr(q, d+1) + P1
+        dn, up = vq[:-1], vq[1:]
+        if cut is not None:
+            link = np.ones(lq.shape[0] - 1, bool)
+            link[np.asarray(cut, dtype=np.int64) - 1] = False
+            dn, up = dn & link[:, None], up & link[:, None]
+        best[1:] = np.minimum(best[1:], np.where(dn, Lq[:-1] + p1, BIG))   # Lr(q, d-1) + P1
+        best[:-1] = np.minimum(best[:-1], np.where(up, Lq[1:] + p1, BIG))   # Lr(q, d+1) + P1
     lr = C + np.where(qnode[None, :], best - m[None, :], 0)
     return np.where(vp, lr, BIG)
 
 
-def path_costs(vol, node, r, p1, p2):
+def path_costs(vol, node, r, p1, p2, cut=None):
     """Lr for direction r = (dx, dy): [nd, h, w] int64, BIG where d is no candidate or the pixel no node."""
     nd, h, w = vol.shape
     dx, dy = r
@@ -76,7 +82,7 @@ def path_costs(vol, node, r, p1, p2):
             if prev is None:
                 lr = np.where(valid[:, :, x], C[:, :, x], BIG)
             else:
-                lr = _step(out[:, :, prev], valid[:, :, prev], node[:, prev], C[:, :, x], valid[:, :, x], p1, p2)
+                lr = _step(out[:, :, prev], valid[:, :, prev], node[:, prev], C[:, :, x], valid[:, :, x], p1, p2, cut)
             out[:, :, x] = lr
             prev = x
         return out
@@ -93,18 +99,18 @@ def path_costs(vol, node, r, p1, p2):
             Lq = out[:, prev, xqc]
             vq = valid[:, prev, xqc] & inside[None]
             qn = node[prev, xqc] & inside
-            out[:, y, :] = _step(Lq, vq, qn, C[:, y, :], valid[:, y, :], p1, p2)
+            out[:, y, :] = _step(Lq, vq, qn, C[:, y, :], valid[:, y, :], p1, p2, cut)
         prev = y
     return out
 
 
-def aggregate(vol, node, paths, p1, p2):
+def aggregate(vol, node, paths, p1, p2, cut=None):
     """S [nd, h, w] int64 (BIG where d is no candidate or the pixel no node) and the largest Lr met."""
     S = np.zeros(vol.shape, dtype=np.int64)
     valid = (vol >= 0) & node[None]
     lmax = 0
     for r in (DIRS4 if paths == 4 else DIRS8):
-        lr = path_costs(vol, node, r, p1, p2)
+        lr = path_costs(vol, node, r, p1, p2, cut)
         if valid.any():
             lmax = max(lmax, int(lr[valid].max()))
         S += np.where(valid, lr, 0)
@@ -112,12 +118,18 @@ def aggregate(vol, node, paths, p1, p2):
 
 
 def sgm_np(L, R, view, block_size, min_disparity, max_disparity, cost="ssd", paths=8, p1=0, p2=0, subpixel=False,
-           return_lmax=False):
-    """The map of an SGM search (float64; with subpixel the float32 values widened)."""
-    vol, d0, node, region, blk = volume(L, R, view, block_size, min_disparity, max_disparity, cost)
+           return_lmax=False, cut=None):
+    """The map of an SGM search (float64; with subpixel the float32 values widened).  cut: see _step; None is the rule."""
+    V = volume(L, R, view, block_size, min_disparity, max_disparity, cost)
+    return sgm_from_volume(V, view, paths, p1, p2, subpixel, return_lmax, cut)
+
+
+def sgm_from_volume(V, view, paths=8, p1=0, p2=0, subpixel=False, return_lmax=False, cut=None):
+    """sgm_np on what volume() returned (left unchanged), for callers that aggregate the same costs more than once."""
+    vol, d0, node, region, blk = V
     nd = vol.shape[0]
     h, w = node.shape
-    S, lmax = aggregate(vol, node, paths, p1, p2)
+    S, lmax = aggregate(vol, node, paths, p1, p2, cut)
     xs = np.broadcast_to(np.arange(w)[None, :], (h, w))
     out = np.zeros((h, w), dtype=np.float64)
     fallback = region & ~blk & ~node

@@ -7,6 +7,7 @@ import pytest
 
 from conftest import load_golden
 from oracle import brute
+from sgm_inputs import GEOMETRIES, geometry_case
 from sgm_ref import sgm_np, sgm_py
 from test_subpixel_reference import shifted_pair
 
@@ -43,6 +44,24 @@ def test_the_two_restatements_agree(seed):
     a = sgm_np(L, R, view, bs, mind, maxd, cost, paths, p1, p2, subpixel=sub)
     b = sgm_py(L, R, view, bs, mind, maxd, cost, paths, p1, p2, subpixel=sub)
     assert a.tobytes() == b.tobytes(), (seed, np.argwhere(a != b)[:5].tolist())
+
+
+@pytest.mark.parametrize("name", sorted(GEOMETRIES))
+def test_the_two_restatements_agree_on_a_larger_right_image(name):
+    """A right image wider than the left one, taller, or both (the right view: wider by more than max_disparity, taller
+    by the one row it may be): the geometries of tests/test_gpu_sgm_forms.py at a size the literal loops can walk."""
+    maxd = 6
+    L, R, view, mind = geometry_case(name, 15, 8, maxd)
+    assert R.shape[1] > L.shape[1] or R.shape[0] > L.shape[0]
+    for i, (bs, cost, paths, p1, p2, sub) in enumerate(((3, "sad", 8, 7, 90, True), (5, "ssd", 4, 40, 900, False))):
+        a = sgm_np(L, R, view, bs, mind, maxd, cost, paths, p1, p2, subpixel=sub)
+        b = sgm_py(L, R, view, bs, mind, maxd, cost, paths, p1, p2, subpixel=sub)
+        assert a.shape == R.shape[:2] if view == "right" else a.shape == L.shape[:2]
+        assert a.tobytes() == b.tobytes(), (name, i, np.argwhere(a != b)[:5].tolist())
+        if view == "right" and R.shape[1] > L.shape[1] + maxd:   # the columns without a candidate hold -x
+            xs = np.arange(L.shape[1], R.shape[1])
+            rows = min(L.shape[0], R.shape[0])
+            assert (a[:rows, L.shape[1]:] == -xs[None, :]).all()
 
 
 def test_the_restatements_are_not_the_block_search():
