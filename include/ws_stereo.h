@@ -50,7 +50,10 @@ enum {
 
 enum {
     WS_COST_SSD = 0, /* the reference's cost: cv::norm(absdiff, NORM_L2) (BlockSearch.cpp:64-66) */
-    WS_COST_SAD = 1  /* extension: NORM_L1 in the same loops (BASELINE.json configs 1 and 3) */
+    WS_COST_SAD = 1, /* extension: NORM_L1 in the same loops (BASELINE.json configs 1 and 3) */
+    /* extension: the Hamming distance of census-transform descriptors ("census-transform matching cost" below) */
+    WS_COST_CENSUS_5X5 = 2, /* 24-bit descriptors: neighbourhood rx = 2, ry = 2 */
+    WS_COST_CENSUS_9X7 = 3  /* 62-bit descriptors: neighbourhood rx = 4, ry = 3 (9 wide, 7 high) */
 };
 
 enum { WS_OUT_F32 = 0, WS_OUT_F64 = 1 }; /* F64 = the reference's CV_64F maps (BlockSearch.cpp:33) */
@@ -117,7 +120,9 @@ typedef struct {
     int passes;                     /* d-group passes (disparity ranges wider than one tile holds) */
     int tile_cols;                  /* columns a tile hands out: x_runs*x_per_thread, one run less for the halo-exchange SAD kernels */
     int kernel_kind;                /* 0: the stencil marching kernel; 1: the int8 matrix-core SSD kernel (a wave owns 32 columns:
-                                       x_runs*x_per_thread is still the tile's width, d_chunks*d_per_thread the candidates a tile holds) */
+                                       x_runs*x_per_thread is still the tile's width, d_chunks*d_per_thread the candidates a tile holds);
+                                       2: the census match kernel (marching 0: it writes the whole map; threads, tiles, strips,
+                                       strip_rows, tile_cols, lds_bytes are its own, d_chunks the 64-lane chunks of the range) */
 } ws_plan_info;
 int ws_plan(const ws_params *p, const ws_image *left, const ws_image *right, int num_cus,
             ws_plan_info *out);
@@ -287,7 +292,7 @@ int ws_last_speckle_counts(ws_context *ctx, unsigned long long counts[2]);
 /* ---- semi-global matching (extension) ---------------------------------------------------- */
 /*
  * Hirschmueller's cost aggregation along image paths over the block search's exact window costs.  p: view LEFT or
- * RIGHT, cost, block_size, the disparity range and subpixel, as for ws_search_*; smooth_factor must be 1.  For each pixel
+ * RIGHT, cost (SSD, SAD or a census cost), block_size, the disparity range and subpixel, as for ws_search_*; smooth_factor must be 1.  For each pixel
  * p of the output map the block search (smoothFactor 1, no varBlock) defines
  *   * K(p): its candidate disparities, a contiguous interval or empty;
  *   * C(p, d) for d in K(p): the exact integer window cost (SSD: the sum of squares before the square root; right view:
@@ -335,6 +340,40 @@ int ws_search_sgm_device(ws_context *ctx, const ws_params *p, const ws_sgm_param
 int ws_search_sgm_host(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *left,
                        const ws_image *right, void *out, int out_stride, int out_dtype);
 
+/* ---- census-transform matching cost (extension) -------------------------------------------- */
+/*
+ * WS_COST_CENSUS_5X5 / WS_COST_CENSUS_9X7 as ws_params.cost: the block search, and semi-global matching over it, on a
+ * cost that does not assume both cameras see the same brightness.
+ *   1. Grey: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14, in integers (14-bit BT.601; the weights sum to 16384, so a grey
+ *      pixel B = G = R = v has Y = v exactly).  No bit-identity with any OpenCV release is claimed.
+ *   2. Descriptor: T(y, x) lists the neighbours (y + dy, x + dx), dy = -ry .. ry outermost, dx = -rx .. rx innermost, the
+ *      centre skipped; bit k (least significant first) belongs to the k-th neighbour and is 1 iff that neighbour lies
+ *      inside the image and Y(neighbour) < Y(centre).  A neighbour outside the image gives 0.  Each image is
+ *      transformed whole, at its own size, whatever the view.  The 5x5 descriptor sits in the low 24 bits.
+ *   3. Pixel term: popcount(T_L(y, x_l) xor T_R(y, x_r)) replaces the SSD / SAD term between L(y, x_l) and R(y, x_r).
+ *   4. Everything else is the block search at smoothFactor 1: the candidate sets K(p), the windows, the black test on
+ *      the view's own BGR pixel, the fallbacks (x / -x / 0) and the tie rules (left view the largest d, right view the
+ *      smallest) are unchanged.  C(p, d) is the integer sum of the pixel term over the window the SGM section defines
+ *      (left view the full block, right view the clipped (left + right) x (up + down) window);
+ *      C <= bits * block_size^2 with bits = 24 or 62, at most 62 * 63^2 = 246078.
+ *   5. Sub-pixel: the parabola of the SGM section on the integer C, with the same float32 rounding.
+ *   6. ws_search_sgm_* takes the census costs with no other rule changed; costs are stored in 16 bits when
+ *      bits * block_size^2 <= 65535 (9x7 up to block_size 31, 5x5 up to 51).  The identity holds: with P1 = P2 = 0 the SGM
+ *      map equals the census block search bit for bit, the sub-pixel map included.
+ *   7. Refusals (ws_validate / ws_validate_sgm, without a device): a census cost with smooth_factor != 1, or with var_block
+ *      in the right view, is WS_ERR_UNSUPPORTED; every other refusal keeps its code; WS_VIEW_LINEAR ignores cost.
+ *   8. Invariance: on grey images, applying one strictly increasing map of 0..255 to either image changes no descriptor
+ *      (rules 1-3), hence no map.
+ * A census call is never cut into row bands (a descriptor looks ry rows beyond the window's halo): ws_search_host
+ * searches it whole, and a batch with a census job is dealt as whole pairs.  Its map crosses PCIe as float32.
+ *
+ * The descriptors on their own: out holds h x w elements, out_stride elements apart (>= width), always 64 bits wide.  A
+ * cost that is not a census value is WS_ERR_ARG.  The device form only enqueues, on `stream` (NULL = the context's own).
+ */
+int ws_census_transform_device(ws_context *ctx, const ws_image *img_dev, int cost, uint64_t *out_dev, int out_stride,
+                               void *stream);
+int ws_census_transform_host(ws_context *ctx, const ws_image *img, int cost, uint64_t *out, int out_stride);
+
 /* ---- many pairs over the devices of a node ------------------------------------------------ */
 /*
  * Independent pairs are dealt to WORKERS: one ws_context and one host thread each.  Workers are device indices; a device
@@ -343,8 +382,8 @@ int ws_search_sgm_host(ws_context *ctx, const ws_params *p, const ws_sgm_params 
  * context, for both out_dtypes and both wire formats.  The assignment restates stereo_reconstruction_amd/sharding.py:
  *   whole pairs (bands == 0, or a batch that cannot be banded): lpt_assign, cost out_w * out_h * nd with
  *     nd = max_disparity (LEFT), max_disparity - min_disparity (RIGHT), linear_range (LINEAR);
- *   row bands (bands == 1): band_items, if every job is LEFT or RIGHT with smoothFactor 1, no varBlock, equal image
- *     heights, and all jobs share block_size and nd (>= 1).  A band is the search of the sub-images
+ *   row bands (bands == 1): band_items, if every job is LEFT or RIGHT with smoothFactor 1, no varBlock, no census cost,
+ *     equal image heights, and all jobs share block_size and nd (>= 1).  A band is the search of the sub-images
  *     [max(0, y0 - half), min(h, y1 + half)); only its map rows [y0, y1) are written to `out`.
  */
 #define WS_JOB_NOT_RUN 1 /* ws_job.status: its worker stopped at an earlier error (or another job was invalid) */

@@ -26,12 +26,14 @@ from . import build as _build
 
 __all__ = ["WindowSearch", "BatchSearch", "BlockSearch", "LinearSearch", "ImageRectifier", "WsError", "load_library", "rectified_size",
            "read_pfm", "write_pfm", "read_ppm", "write_ppm", "write_mesh_off", "read_calib", "evaldisp", "VIEW_LEFT", "VIEW_RIGHT",
-           "VIEW_LINEAR", "COST_SSD", "COST_SAD"]
+           "VIEW_LINEAR", "COST_SSD", "COST_SAD", "COST_CENSUS_5X5", "COST_CENSUS_9X7"]
 
 VIEW_LEFT, VIEW_RIGHT, VIEW_LINEAR = 0, 1, 2
 COST_SSD, COST_SAD = 0, 1
+COST_CENSUS_5X5, COST_CENSUS_9X7 = 2, 3  # the Hamming distance of census-transform descriptors (rules in include/ws_stereo.h)
 OUT_F32, OUT_F64 = 0, 1
-_COST = {"ssd": COST_SSD, "sad": COST_SAD, COST_SSD: COST_SSD, COST_SAD: COST_SAD}
+_COST = {"ssd": COST_SSD, "sad": COST_SAD, "census5x5": COST_CENSUS_5X5, "census9x7": COST_CENSUS_9X7,
+         COST_SSD: COST_SSD, COST_SAD: COST_SAD, COST_CENSUS_5X5: COST_CENSUS_5X5, COST_CENSUS_9X7: COST_CENSUS_9X7}
 
 ERRORS = {-1: "WS_ERR_ARG", -2: "WS_ERR_GEOMETRY", -3: "WS_ERR_UNSUPPORTED", -4: "WS_ERR_HIP",
           -5: "WS_ERR_IO", -6: "WS_ERR_NOMEM"}
@@ -48,7 +50,8 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_batch_create", "ws_batch_destroy", "ws_batch_last_error", "ws_batch_workers", "ws_batch_plan",
            "ws_batch_search_host", "ws_lr_check_device", "ws_search_lr_host", "ws_search_lr_device", "ws_last_lr_counts",
            "ws_filter_speckles_device", "ws_filter_speckles_host", "ws_last_speckle_counts",
-           "ws_validate_sgm", "ws_sgm_scratch_bytes", "ws_search_sgm_device", "ws_search_sgm_host"]
+           "ws_validate_sgm", "ws_sgm_scratch_bytes", "ws_search_sgm_device", "ws_search_sgm_host",
+           "ws_census_transform_device", "ws_census_transform_host"]
 JOB_NOT_RUN = 1  # ws_job.status of a job its worker never reached (WS_JOB_NOT_RUN)
 
 
@@ -264,6 +267,8 @@ def load_library(build_if_missing=False):
     lib.ws_sgm_scratch_bytes.argtypes = [P(_Params), P(_SgmParams), P(_Image), P(_Image), P(ctypes.c_ulonglong)]
     lib.ws_search_sgm_device.argtypes = [vp, P(_Params), P(_SgmParams), P(_Image), P(_Image), vp, ci, vp]
     lib.ws_search_sgm_host.argtypes = [vp, P(_Params), P(_SgmParams), P(_Image), P(_Image), vp, ci, ci]
+    lib.ws_census_transform_device.argtypes = [vp, P(_Image), ci, vp, ci, vp]
+    lib.ws_census_transform_host.argtypes = [vp, P(_Image), ci, vp, ci]
     _lib = lib
     return lib
 
@@ -448,6 +453,24 @@ class WindowSearch:
         self._check(self._lib.ws_search_sgm_device(self._h, ctypes.byref(params), ctypes.byref(sp), ctypes.byref(Li),
                                                    ctypes.byref(Ri), out_t.data_ptr(), out_t.stride(0),
                                                    ctypes.c_void_p(stream or 0)))
+
+    # -- census transform (extension; rules in include/ws_stereo.h) -------------------------------
+    def census_transform(self, img, cost):
+        """ws_census_transform_host: the census descriptors of a BGR image (H x W x 3 uint8) as an H x W uint64 array;
+        cost is COST_CENSUS_5X5 / COST_CENSUS_9X7 or "census5x5" / "census9x7"."""
+        a, hdr = _host_image(img)
+        out = np.empty(a.shape[:2], dtype=np.uint64)
+        self._check(self._lib.ws_census_transform_host(self._h, ctypes.byref(hdr), _COST[cost], out.ctypes.data, out.shape[1]))
+        return out
+
+    def census_transform_device(self, img_t, cost, out_t, stream=None):
+        """ws_census_transform_device on a uint8 CUDA image H x W x 3 into a 64-bit integer CUDA tensor H x W (rows may
+        be padded).  Only enqueues on `stream` (as search_device)."""
+        if out_t.dim() != 2 or out_t.stride(1) != 1 or out_t.element_size() != 8 or out_t.is_floating_point():
+            raise ValueError("expected a 64-bit integer H x W tensor with dense rows")
+        Ii = _Image(img_t.data_ptr(), img_t.shape[1], img_t.shape[0], img_t.stride(0))
+        self._check(self._lib.ws_census_transform_device(self._h, ctypes.byref(Ii), _COST[cost], out_t.data_ptr(),
+                                                         out_t.stride(0), ctypes.c_void_p(stream or 0)))
 
     # -- speckle filter (extension; rules in include/ws_stereo.h) ---------------------------------
     def filter_speckles(self, disparity, new_val=0.0, max_speckle_size=100, max_diff=1.0):

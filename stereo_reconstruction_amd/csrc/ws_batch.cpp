@@ -46,11 +46,13 @@ long long job_nd(const ws_params &p)
                                    : (long long)p.linear_range;
 }
 
-// ws_search_host's own test for cutting a call into bands (ws_capi.cpp): no raster dependency, no varBlock growth
+// ws_search_host's own test for cutting a call into bands (ws_capi.cpp): no raster dependency, no varBlock growth, no
+// census cost (its descriptors look ry rows beyond the window's halo); sharding.can_band restates it
 bool band_ok(const ws_job &j)
 {
+    const bool census = j.params.cost == WS_COST_CENSUS_5X5 || j.params.cost == WS_COST_CENSUS_9X7;
     return (j.params.view == WS_VIEW_LEFT || j.params.view == WS_VIEW_RIGHT) && j.params.smooth_factor == 1.0 &&
-           !j.params.var_block && j.left.height == j.right.height;
+           !j.params.var_block && !census && j.left.height == j.right.height;
 }
 
 // The checks of one job: its parameters and images as ws_validate checks them, and (outputs) its map buffer as

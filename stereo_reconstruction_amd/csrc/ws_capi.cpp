@@ -4,6 +4,7 @@
 // left-right check's entry points are in ws_lr.cpp, the speckle filter's in ws_speckle.cpp.
 // The Middlebury plumbing (PFM, calib.txt, evaldisp) is in ws_io.cpp.
 #include "../../include/ws_stereo.h"
+#include "ws_ct.h"
 #include "ws_kernels.h"
 #include "ws_rectify.h"
 #include "ws_search.h"
@@ -186,6 +187,20 @@ int ws_plan(const ws_params *p, const ws_image *left, const ws_image *right, int
     memset(out, 0, sizeof *out);
     int rc = check_params(nullptr, p, left, right);
     if (rc != WS_OK) return rc;
+    if (p->view != WS_VIEW_LINEAR && is_census(p->cost)) { // the census match kernel: no marching region, one kernel for the map
+        const int ow = p->view == WS_VIEW_LEFT ? left->width : right->width, oh = p->view == WS_VIEW_LEFT ? left->height : right->height;
+        int d0, nd;
+        census_range(p, left, &d0, &nd);
+        out->kernel_kind = 2;
+        out->threads = kCtThreads;
+        out->tiles = (ow + kCtTile - 1) / kCtTile;
+        out->strips = (oh + kCtStrip - 1) / kCtStrip;
+        out->strip_rows = kCtStrip;
+        out->tile_cols = kCtTile;
+        out->d_chunks = (nd + kCtWtaStep - 1) / kCtWtaStep;
+        out->lds_bytes = kCtLdsWta;
+        return WS_OK;
+    }
     Canon c{};
     MarchLaunch m{};
     if (make_canon(p, left, right, &c) && march_plan(c, num_cus > 0 ? num_cus : 256, 0, 0, 0, &m)) {
@@ -346,7 +361,9 @@ int ws_search_host(ws_context *ctx, const ws_params *p, const ws_image *left, co
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // bands pay when the copies are worth hiding and each band still fills the chip
-    const bool can = (p->view == WS_VIEW_LEFT || p->view == WS_VIEW_RIGHT) && p->smooth_factor == 1.0 && !p->var_block &&
+    // (a census descriptor looks ry rows beyond the window: a band would see "outside the image" there, so a census call
+    // is never cut)
+    const bool can = (p->view == WS_VIEW_LEFT || p->view == WS_VIEW_RIGHT) && p->smooth_factor == 1.0 && !p->var_block && !is_census(p->cost) &&
                      left->height == right->height && out_stride == ow && linear_span(left) && linear_span(right) &&
                      (size_t)left->stride <= 2 * (size_t)left->width * 3 && (size_t)right->stride <= 2 * (size_t)right->width * 3;
     int nb = ctx->host_bands;
@@ -934,6 +951,50 @@ int ws_reconstruction_host(ws_context *ctx, const float *depth, int width, int h
     }();
     rc = finish_host_call(ctx, rc, sp, 2, {s}, "reconstruction");
     return mesh_close(ctx, rc, f, s);
+}
+
+// ---- the census transform on its own (the searches run it on the Searcher's planes) --------------------------------
+
+static int census_transform_args(std::string *err, const ws_image *img, int cost, const void *out, int out_stride)
+{
+    if (!image_ok(img)) return fail(err, WS_ERR_ARG, "null or malformed image");
+    if (!is_census(cost)) return fail(err, WS_ERR_ARG, "cost %d is not a census cost", cost);
+    if (!out) return fail(err, WS_ERR_ARG, "null output");
+    if (out_stride < img->width) return fail(err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, img->width);
+    return WS_OK;
+}
+
+int ws_census_transform_device(ws_context *ctx, const ws_image *img_dev, int cost, uint64_t *out_dev, int out_stride, void *stream)
+{
+    if (!ctx) return WS_ERR_ARG;
+    if (const int rc = census_transform_args(&ctx->err, img_dev, cost, out_dev, out_stride); rc != WS_OK) return rc;
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    WS_HIP(&ctx->err, launch_census_transform(img_dev->data, img_dev->width, img_dev->height, img_dev->stride, cost, out_dev, out_stride, true, s));
+    return WS_OK;
+}
+
+int ws_census_transform_host(ws_context *ctx, const ws_image *img, int cost, uint64_t *out, int out_stride)
+{
+    if (!ctx) return WS_ERR_ARG;
+    int rc = census_transform_args(&ctx->err, img, cost, out, out_stride);
+    if (rc != WS_OK) return rc;
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t w = (size_t)img->width, h = (size_t)img->height;
+    HostSpan sp[2];
+    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], img, &ctx->h_left))) != WS_OK) return rc;
+    if ((rc = ensure(&ctx->err, ctx->d_out64, w * h * 8)) != WS_OK) return rc;
+    span_set(sp[1], out, (size_t)out_stride * 8, w * 8, h, &ctx->h_out);
+    spans_attach(sp, 2);
+    rc = [&]() -> int {
+        ws_image di;
+        WS_HIP(&ctx->err, upload_image(sp[0], img, static_cast<uint8_t *>(ctx->d_left.p), s, &di));
+        WS_HIP(&ctx->err, launch_census_transform(di.data, di.width, di.height, di.stride, cost, ctx->d_out64.p, di.width, true, s));
+        WS_HIP(&ctx->err, span_download_bytes(sp[1], 0, (size_t)out_stride * 8, ctx->d_out64.p, w * 8, h, s));
+        return WS_OK;
+    }();
+    return finish_host_call(ctx, rc, sp, 2, {s}, "census transform");
 }
 
 int ws_timer_begin(ws_context *ctx, void *stream)

@@ -1,6 +1,7 @@
 // ws_search.cpp -- argument checks that stand in for the reference's cv::Exception paths, reduction of the three
 // reference methods to the canonical search (ws_kernels.h), and the launches of one search (ws_search.h).
 #include "ws_search.h"
+#include "ws_ct.h"
 #include "ws_staging.h"
 
 #include <string.h>
@@ -143,6 +144,33 @@ int run_canonical(Searcher &S, std::string *err, const ws_params *p, const ws_im
     return WS_OK;
 }
 
+// A census-transform cost (smoothFactor 1, no varBlock: check_params): both images' descriptors into the Searcher's
+// planes, then the match kernel, which writes the whole map itself -- winners, fallbacks, zeros and the parabola.
+int run_census(Searcher &S, std::string *err, const ws_params *p, const ws_image *L, const ws_image *R, float *out, int out_stride,
+               hipStream_t s)
+{
+    const int ow = p->view == WS_VIEW_LEFT ? L->width : R->width, oh = p->view == WS_VIEW_LEFT ? L->height : R->height;
+    if (out_stride < ow) return fail(err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
+    const size_t esz = census_plane_elem(p->cost);
+    int rc;
+    if ((rc = ensure(err, S.ct_left, (size_t)L->width * L->height * esz)) != WS_OK) return rc;
+    if ((rc = ensure(err, S.ct_right, (size_t)R->width * R->height * esz)) != WS_OK) return rc;
+    WS_HIP(err, launch_census_transform(L->data, L->width, L->height, L->stride, p->cost, S.ct_left.p, L->width, false, s));
+    WS_HIP(err, launch_census_transform(R->data, R->width, R->height, R->stride, p->cost, S.ct_right.p, R->width, false, s));
+    CtMatchArgs a = census_match_args(p, L, R, S.ct_left.p, S.ct_right.p);
+    a.out = out;
+    a.out_pitch = out_stride;
+    if (S.profiling) WS_HIP(err, hipEventRecord(S.evk0, s));
+    WS_HIP(err, launch_census_match(a, false, s));
+    if (S.profiling) {
+        WS_HIP(err, hipEventRecord(S.evk1, s));
+        S.kernel_timed = true;
+    }
+    if (p->view == WS_VIEW_RIGHT) S.var_block_ran = false;
+    S.launched(kCtMatchKernel, kCtThreads, (int)census_match_workgroups(ow, oh), kCtLdsWta);
+    return WS_OK;
+}
+
 // smoothFactor: the data-parallel search (smoothFactor 1) first, then the smoothFactor passes on its map.  For the right
 // view and LinearSearch the factor can only reach d = 0 beside a zero-valued neighbour (see ws_smooth.hip), and only
 // when d = 0 is a candidate at all.
@@ -152,6 +180,7 @@ int search_on(Searcher &S, std::string *err, const ws_params *p, const ws_image 
     ws_params q = *p;
     SearchResult r;
     if (q.view == WS_VIEW_LINEAR) q.min_disparity = 0;
+    if (q.view != WS_VIEW_LINEAR && is_census(q.cost)) return run_census(S, err, &q, L, R, out, out_stride, s);
     const bool left = q.view == WS_VIEW_LEFT;
     if (q.smooth_factor == 1.0 || (!left && q.min_disparity != 0))
         return run_canonical(S, err, &q, L, R, out, out_stride, out16, false, false, s, &r);
@@ -208,7 +237,7 @@ int check_params(std::string *err, const ws_params *p, const ws_image *L, const 
     if (!p || !image_ok(L) || !image_ok(R)) return fail(err, WS_ERR_ARG, "null or malformed image / params");
     if (p->view != WS_VIEW_LEFT && p->view != WS_VIEW_RIGHT && p->view != WS_VIEW_LINEAR)
         return fail(err, WS_ERR_ARG, "unknown view %d", p->view);
-    if (p->cost != WS_COST_SSD && p->cost != WS_COST_SAD) return fail(err, WS_ERR_ARG, "unknown cost %d", p->cost);
+    if (p->cost != WS_COST_SSD && p->cost != WS_COST_SAD && !is_census(p->cost)) return fail(err, WS_ERR_ARG, "unknown cost %d", p->cost);
     if (p->view != WS_VIEW_LINEAR && (p->block_size < 1 || p->block_size > 63))
         return fail(err, WS_ERR_ARG, "blockSize %d outside [1,63]", p->block_size);
     if (p->view == WS_VIEW_LINEAR && p->linear_range < 1) return fail(err, WS_ERR_ARG, "linear_range < 1");
@@ -219,6 +248,8 @@ int check_params(std::string *err, const ws_params *p, const ws_image *L, const 
         return fail(err, WS_ERR_ARG, "thres is NaN");
     if (p->subpixel && p->view == WS_VIEW_LINEAR) return fail(err, WS_ERR_UNSUPPORTED, "sub-pixel on LinearSearch");
     if (p->subpixel && p->smooth_factor != 1.0) return fail(err, WS_ERR_UNSUPPORTED, "sub-pixel refinement together with smoothFactor != 1");
+    // (LinearSearch ignores the cost; the refusals the reference's own rules make come first and keep their codes)
+    const bool census = is_census(p->cost) && p->view != WS_VIEW_LINEAR;
     const int h1 = L->height, w1 = L->width, h2 = R->height;
     const int height = std::min(h1, h2);
     const int half = (p->block_size - 1) / 2;
@@ -242,6 +273,8 @@ int check_params(std::string *err, const ws_params *p, const ws_image *L, const 
             return fail(err, WS_ERR_GEOMETRY, "varBlock with a right image taller than the left one: a grown window "
                                               "would leave the left image (BlockSearch.cpp:151-154)");
     }
+    if (census && p->smooth_factor != 1.0) return fail(err, WS_ERR_UNSUPPORTED, "a census cost together with smoothFactor != 1");
+    if (census && p->view == WS_VIEW_RIGHT && p->var_block) return fail(err, WS_ERR_UNSUPPORTED, "a census cost together with varBlock");
     return WS_OK;
 }
 
@@ -262,6 +295,7 @@ bool make_canon(const ws_params *p, const ws_image *L, const ws_image *R, Canon 
     const int half = (p->block_size - 1) / 2;
     Canon k{};
     k.ssd = p->cost == WS_COST_SSD;
+    if (is_census(p->cost) && p->view != WS_VIEW_LINEAR) return false; // (the census match kernel owns the whole map)
     if (p->view == WS_VIEW_LEFT) {
         k.wa = w1; k.ha = h1; k.wb = w2; k.hb = h2;
         k.ww = k.wh = p->block_size;
@@ -302,6 +336,7 @@ bool make_canon(const ws_params *p, const ws_image *L, const ws_image *R, Canon 
 // LinearSearch.cpp:53: col - j), so |value| < max(w1, w2): images up to 32767 pixels wide fit.  Else float32.
 int wire_for(const ws_params *p, const ws_image *L, const ws_image *R)
 {
+    if (p->view != WS_VIEW_LINEAR && is_census(p->cost)) return kWireF32; // (the match kernel stores float32 only)
     const bool writes_only = p->smooth_factor == 1.0 && !p->subpixel && !(p->var_block && p->view == WS_VIEW_RIGHT);
     const bool fits = L->width <= 32767 && R->width <= 32767;
     return writes_only && fits ? kWireI16 : kWireF32;

@@ -11,6 +11,7 @@ namespace wsamd {
 struct Searcher {
     int num_cus = 256; // the device's, for the planner
     DevBuf plane_a, plane_b, keys, cost, bs_plane, max_block, sel, sel_planes, top3;
+    DevBuf ct_left, ct_right; // a census cost: the descriptor planes of both images (ws_ct.h)
     // the last few problems' plans, keyed on (Canon, tuning): a queue of equal pairs asks for the same one every call, the
     // left-right check for two in turn, and the planner walks every strip count for two thread shapes, up to three
     // candidate tilings and two workgroup sizes -- 5 us of a 15 us enqueue

@@ -2,6 +2,7 @@
 // host's bound, the context's scratch for it (SgmState), and the launches of ws_sgm.hip on device memory or on the
 // caller's host buffers (through ws_staging.h).
 #include "ws_context.h"
+#include "ws_ct.h"
 #include "ws_sgm.h"
 
 #include <stdint.h>
@@ -44,10 +45,10 @@ int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, co
 }
 
 // The scratch of one call: the candidate intervals, the cost plane and the sums, each 256-byte aligned.  Storage
-// widths from the bound: C <= Cmax = 3 (255 or 255^2) bs^2 < 2^30; Lr <= C + P2 < 2^32; S <= paths (Cmax + P2).
+// widths from the bound: C <= Cmax = 3 (255 or 255^2) bs^2 < 2^30 (a census cost: 24 or 62 bs^2); Lr <= C + P2 < 2^32; S <= paths (Cmax + P2).
 struct Layout {
     int d0 = 0, nd = 0, w = 0, h = 0, cost16 = 0, sum64 = 0;
-    size_t off_cost = 0, off_sum = 0, bytes = 0;
+    size_t off_cost = 0, off_sum = 0, off_tl = 0, off_tr = 0, bytes = 0; // (off_tl, off_tr: a census cost's descriptor planes)
 };
 
 Layout layout(const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R)
@@ -56,7 +57,7 @@ Layout layout(const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, c
     disparity_range(p, L, &y.d0, &y.nd);
     y.w = p->view == WS_VIEW_LEFT ? L->width : R->width;
     y.h = p->view == WS_VIEW_LEFT ? L->height : R->height;
-    const uint64_t cmax = sgm_cost_max(p->cost == WS_COST_SSD, p->block_size);
+    const uint64_t cmax = sgm_cost_max(p->cost, p->block_size);
     y.cost16 = cmax <= 0xffffu;
     y.sum64 = (uint64_t)sgm->paths * (cmax + (uint64_t)sgm->p2) > 0xffffffffull;
     const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
@@ -64,6 +65,12 @@ Layout layout(const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, c
     y.off_cost = up(px * 4);
     y.off_sum = y.off_cost + up(vol * (y.cost16 ? 2 : 4));
     y.bytes = y.off_sum + up(vol * (y.sum64 ? 8 : 4));
+    if (is_census(p->cost)) {
+        const size_t esz = census_plane_elem(p->cost);
+        y.off_tl = y.bytes;
+        y.off_tr = y.off_tl + up((size_t)L->width * L->height * esz);
+        y.bytes = y.off_tr + up((size_t)R->width * R->height * esz);
+    }
     return y;
 }
 
@@ -133,6 +140,13 @@ int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, c
     a.cost = base + y.off_cost;
     a.sum = base + y.off_sum;
     a.cost16 = y.cost16; a.sum64 = y.sum64;
+    if (is_census(p->cost)) {
+        a.TL = base + y.off_tl;
+        a.TR = base + y.off_tr;
+        a.census_wide = p->cost == WS_COST_CENSUS_9X7;
+        WS_HIP(&ctx->err, launch_census_transform(L->data, L->width, L->height, L->stride, p->cost, base + y.off_tl, L->width, false, s));
+        WS_HIP(&ctx->err, launch_census_transform(R->data, R->width, R->height, R->stride, p->cost, base + y.off_tr, R->width, false, s));
+    }
     a.subpixel = p->subpixel != 0;
     a.out = out;
     a.out_pitch = out_stride;

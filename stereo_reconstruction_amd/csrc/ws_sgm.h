@@ -2,6 +2,8 @@
 // include/ws_stereo.h.
 #pragma once
 
+#include "../../include/ws_stereo.h"
+
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -18,6 +20,8 @@ struct SgmArgs {
     int w1, h1, s1, w2, h2, s2;
     int right;  // 0: left view, 1: right view
     int ssd;
+    const void *TL, *TR; // a census cost: the descriptor planes of both images (ws_ct.h), else null
+    int census_wide;     // ... of 64 bits (9x7) or 32 (5x5)
     int half;   // (block_size - 1) / 2
     int d0, nd; // d = d0 + j for j < nd (nd already clipped to what the geometry allows)
     int w, h;   // the map
@@ -31,10 +35,15 @@ struct SgmArgs {
     int out_pitch;
 };
 
-// The largest window cost of a search (a square window of bs x bs pixels, three channels).
-inline uint64_t sgm_cost_max(int ssd, int block_size) { return 3ull * (ssd ? 65025ull : 255ull) * (uint64_t)block_size * block_size; }
+// The largest window cost of a search with cost WS_COST_* (a square window of bs x bs pixels: three channels, or the bits
+// of a census descriptor).
+inline uint64_t sgm_cost_max(int cost, int block_size)
+{
+    const uint64_t px = cost == WS_COST_SSD ? 3ull * 65025ull : cost == WS_COST_SAD ? 3ull * 255ull : cost == WS_COST_CENSUS_5X5 ? 24ull : 62ull;
+    return px * (uint64_t)block_size * block_size;
+}
 
-// The cost plane, the paths (`paths` 4 or 8, one launch each, summed in place in order on s) and the winner.
+// The cost plane (a census cost: from the match kernel of ws_ct.hip), the paths (`paths` 4 or 8, one launch each, summed in place in order on s) and the winner.
 hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s);
 
 } // namespace wsamd

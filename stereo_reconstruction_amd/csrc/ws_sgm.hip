@@ -15,6 +15,7 @@
 //     the fallbacks; lane 0 writes the float32 value.
 // Every store is a plain vector store.
 #include "ws_sgm.h"
+#include "ws_ct.h"
 
 namespace wsamd {
 
@@ -334,7 +335,14 @@ hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s)
     if (a.nd > 0) {
         const long long blocks = (long long)((a.w + kSgmTile - 1) / kSgmTile) * ((a.nd + 63) / 64) * ((a.h + kSgmStrip - 1) / kSgmStrip);
         if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-        if (a.cost16) ws_sgm_cost_kernel<uint16_t><<<(int)blocks, kSgmThreads, 0, s>>>(a);
+        if (a.TL) { // a census cost: the one implementation of its window sums, storing C in this layout
+            CtMatchArgs c{};
+            c.TL = a.TL; c.TR = a.TR; c.L = a.L; c.R = a.R;
+            c.w1 = a.w1; c.h1 = a.h1; c.s1 = a.s1; c.w2 = a.w2; c.h2 = a.h2; c.s2 = a.s2;
+            c.wide = a.census_wide; c.right = a.right; c.half = a.half; c.d0 = a.d0; c.nd = a.nd; c.w = a.w; c.h = a.h;
+            c.cost = a.cost; c.cost16 = a.cost16;
+            if (const hipError_t e = launch_census_match(c, true, s); e != hipSuccess) return e;
+        } else if (a.cost16) ws_sgm_cost_kernel<uint16_t><<<(int)blocks, kSgmThreads, 0, s>>>(a);
         else ws_sgm_cost_kernel<uint32_t><<<(int)blocks, kSgmThreads, 0, s>>>(a);
         hipError_t e;
         if (a.cost16 && !a.sum64) e = launch_paths_nj<uint16_t, uint32_t>(a, paths, s);

@@ -127,7 +127,8 @@ public:
     {
     }
 
-    int cost = WS_COST_SSD; // the reference's NORM_L2
+    int cost = WS_COST_SSD; // the reference's NORM_L2; WS_COST_SAD, or WS_COST_CENSUS_5X5 / WS_COST_CENSUS_9X7 (the Hamming
+                            // distance of census-transform descriptors, smoothFactor 1 only; rules in ws_stereo.h)
     bool subpixel = false;
 
     MatF64 computeDisparityMapLeft(double smoothFactor) // BlockSearch.cpp:24-86
@@ -342,7 +343,7 @@ public:
     const double *getH_() const { return H_; }
     const double *getHp_() const { return Hp_; }
 
-    int cost = WS_COST_SSD; // the build's extensions, as on BlockSearch
+    int cost = WS_COST_SSD; // the build's extensions, as on BlockSearch (WS_COST_CENSUS_5X5 / _9X7 included)
     bool subpixel = false;
 
 private:
@@ -411,6 +412,17 @@ inline void filterSpeckles(MatF32 &img, double newVal, int maxSpeckleSize, doubl
     sp.max_diff = static_cast<float>(maxDiff);
     const int rc = ws_filter_speckles_host(device.get(), img.ptr(), img.cols, img.rows, img.cols, &sp);
     if (rc != WS_OK) throw Error(rc, ws_last_error(device.get()));
+}
+
+// Extension: the census-transform descriptors of an image (rules in ws_stereo.h), row-major, img.cols per row; cost is
+// WS_COST_CENSUS_5X5 (24 bits) or WS_COST_CENSUS_9X7 (62 bits).
+inline std::vector<uint64_t> censusTransform(const Image8UC3 &img, int cost, Device &device = Device::shared())
+{
+    std::vector<uint64_t> out(static_cast<size_t>(img.rows > 0 ? img.rows : 0) * static_cast<size_t>(img.cols > 0 ? img.cols : 0));
+    const ws_image im = detail::to_c(img);
+    const int rc = ws_census_transform_host(device.get(), &im, cost, out.data(), img.cols);
+    if (rc != WS_OK) throw Error(rc, ws_last_error(device.get()));
+    return out;
 }
 
 inline MatF32 convertDisparityToDepth(const MatF32 &dispImage, float focalLength, float baseline,

@@ -11,9 +11,17 @@ Work items are whole pairs (`lpt_assign`) or, for smoothFactor 1, ROW BANDS of p
 sub-images [y0 - half, y1 + half) -- what ws_search_host's own banded path relies on, results
 identical.  15 trainingH pairs as whole items balance to 1.13 x / 1.15 x the mean at 4 / 8
 ranks; as bands of >= 256 rows to <= 1.03 x.  smoothFactor != 1 (a raster dependency down the
-whole image) and varBlock keep whole pairs.
+whole image) and varBlock keep whole pairs, and so does a census cost: its descriptors look ry rows
+beyond the window's halo (`can_band`).
 """
 import time
+
+
+def can_band(view, smooth_factor, var_block, cost, left_rows, right_rows):
+    """May a pair with these parameters be cut into row bands?  Restates band_ok of csrc/ws_batch.cpp (and
+    ws_search_host's own test): LEFT (0) or RIGHT (1) view, smoothFactor 1, no varBlock, not a census cost (2, 3),
+    equal image heights."""
+    return view in (0, 1) and smooth_factor == 1.0 and not var_block and cost not in (2, 3) and left_rows == right_rows
 
 
 def lpt_assign(costs, world):
