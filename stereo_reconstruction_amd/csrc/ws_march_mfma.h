@@ -22,12 +22,18 @@
 //
 // Geometry: a workgroup of 8 waves owns a tile of 128 columns and a strip of rows; two waves share columns 32 wx .. 32 wx + 31
 // and split their NV tiles of 32 target centres (NV = 9 covers 256 disparities) 5 : 4, each with its 16 accumulators per
-// tile in registers for the whole strip; the second wave hands its best candidate to the first through LDS, which writes
+// tile in registers for the whole strip; the first wave hands its best candidate to the second through LDS, which writes
 // the row out one step later.
 // Rows travel HBM -> LDS as the bytes they are (raw_dma of ws_march_kernel.h) into a ring of WH + 4 raw rows per
-// image, three stages ahead of their use, one barrier per step:
-//   step s:  copy row s + 3  |  xor row s + 2 with 0x80 in place  |  row s + 1: bias' values, the target row as lane-linear
-//            MFMA operands (a ring of WH + 2 rows of 12 KB)  |  MFMAs, keys of row s, output of row s - 1.
+// image, and stay raw: every consumer centres the bytes in an instruction it issues anyway.  One barrier per step:
+//   step s:  copy row s + 3  |  (row s + 2 rests: the copies' look-ahead)  |  row s + 1 of the target image: one pass
+//            makes its lane-linear MFMA operands (a ring of WH + 2 rows of 12 KB) and, from the same registers, the
+//            bias' values  |  MFMAs, keys of row s, output of row s - 1.
+// The step ends when its slowest wave reaches the barrier, so the roles are dealt by tile share: the waves with 5 tiles
+// (wv = 0) take one block of the operand pass each and waves 0 and 1 the copies, the waves with 4 tiles (wv = 1) take
+// two blocks each, the merge of the two waves' candidates and the store of the output row.  A wave's role is a template
+// argument of its march, the rows' ring offsets and byte phases are scalars advanced with a compare and a wrap, and the
+// steady phase of a strip has no guard: its LDS reads are issued together, ahead of the first wait on any of them.
 #pragma once
 #include "ws_march_kernel.h"
 
@@ -89,6 +95,39 @@ __device__ __forceinline__ ws_i32x4 mfma_operand(uint32_t row, uint32_t p)
     return r;
 }
 
+// 16 bytes from LDS byte address t (any alignment): 5 dword reads now, 4 v_alignbyte when the bytes are needed
+struct MfmaRaw {
+    uint32_t d0, d1, d2, d3, d4, sh;
+};
+__device__ __forceinline__ MfmaRaw mfma_raw_load(uint32_t t)
+{
+    const lds_u32 *q = lds_at32(t & ~3u);
+    return MfmaRaw{q[0], q[1], q[2], q[3], q[4], t & 3u};
+}
+__device__ __forceinline__ ws_i32x4 mfma_raw_align(const MfmaRaw &r)
+{
+    ws_i32x4 v;
+    v.x = (int)__builtin_amdgcn_alignbyte(r.d1, r.d0, r.sh);
+    v.y = (int)__builtin_amdgcn_alignbyte(r.d2, r.d1, r.sh);
+    v.z = (int)__builtin_amdgcn_alignbyte(r.d3, r.d2, r.sh);
+    v.w = (int)__builtin_amdgcn_alignbyte(r.d4, r.d3, r.sh);
+    return v;
+}
+
+// lane n and lane n + 32 both get the sum of their two values: one v_permlane32_swap
+__device__ __forceinline__ uint32_t mfma_pair_sum(uint32_t x)
+{
+    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return r[0] + r[1];
+}
+
+// a ring cursor: on by one row, back to the ring's first row behind its last
+__device__ __forceinline__ void mfma_advance(uint32_t &at, uint32_t row, uint32_t end)
+{
+    at += row;
+    at = at == end ? 0u : at;
+}
+
 template <int WW, int WH>
 __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const MarchArgs g)
 {
@@ -96,10 +135,10 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
     constexpr int NR = mfma_ring_rows(WH);
     constexpr int K = 3 * WW;
     static_assert(K <= 32 && K > 16, "one row of the window is one K = 32 step, its pad in the upper lane half");
-    static_assert(TX + 32 * (NV - 1) <= NT, "one bias value per thread");
     // a centred cost word sum b^^2 - 2 sum a^.b^ lies in [-128^2, 128^2 + 2 * 127 * 128] per byte of the window
     static_assert((long long)(128 * 128 + 2 * 127 * 128) * K * WH * (1 << KT) < (long long)kValidKeyBound, "keys stay inside (-2^28, 2^28)");
     static_assert(kPoison % (1 << (KT + 1)) == 0, "the poison survives the shift");
+    static_assert(kMfmaXWaves == 4 && kMfmaVWaves == 2, "wave >> 2 is the share of the tiles");
 
     extern __shared__ uint4 ws_smem4[];
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_u32 *)reinterpret_cast<uint32_t *>(ws_smem4);
@@ -113,7 +152,6 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31, h = lane >> 5;
     const int wx = wave & (kMfmaXWaves - 1), wv = wave >> 2; // this wave's 32 columns, its share of their tiles: t = wv NVW + j
-    static_assert(kMfmaXWaves == 4, "wave >> 2");
 
     const int nblk = gridDim.x; // padded to a multiple of 8 by the launcher: every XCD a contiguous range of (strip, tile) pairs
     const int logical = (blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
@@ -142,8 +180,9 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
         if (last_t && g.out_w > g.ox1) zero_rect(g.ox1, g.out_w, ys, ye);
     }
 
-    // the rings start as zeros: bytes outside the image are never copied, and whatever they hold they hold for a row's
-    // whole life (the candidates that read them are poisoned, their keys stay bounded because they are bytes)
+    // the raw rings start as zeros: bytes outside the image are never copied and stay zero, which every consumer reads
+    // as the centred byte -128 for the row's whole life (the candidates that read them are poisoned, their keys stay
+    // bounded because -128 is a byte like any other: the first static_assert above)
     for (int k = tid; k < L.o_bias / 16; k += NT) lds_store128(lds0 + 16u * (uint32_t)k, make_uint4(0u, 0u, 0u, 0u));
 
     const int dspan = g.d_hi - g.d_lo;
@@ -158,38 +197,34 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
     const uint32_t phA0 = (uint32_t)(reinterpret_cast<uintptr_t>(sideA.base) + (uintptr_t)((long long)ra0 * sideA.stride + 3LL * sideA.c0)) & 15u;
     const uint32_t phB0 = (uint32_t)(reinterpret_cast<uintptr_t>(sideB.base) + (uintptr_t)((long long)ra0 * sideB.stride + 3LL * sideB.c0)) & 15u;
     const uint32_t stA = (uint32_t)sideA.stride & 15u, stB = (uint32_t)sideB.stride & 15u;
-    // strip row i (any i >= -NR): its ring slot and the byte phase of raw index 0 in it
-    auto slot_of = [&](int i) __attribute__((always_inline)) { return (uint32_t)(i + NR) % (uint32_t)NR; };
-    auto opslot_of = [&](int i) __attribute__((always_inline)) { return (uint32_t)(i + 2 * NRO) % (uint32_t)NRO; };
-    auto phase_a = [&](int i) __attribute__((always_inline)) { return (phA0 + (uint32_t)i * stA) & 15u; };
-    auto phase_b = [&](int i) __attribute__((always_inline)) { return (phB0 + (uint32_t)i * stB) & 15u; };
 
-    // ---- this thread's bias value: target centre vb0 + tid ----------------------------------------------------
-    // tag: register i of a tile holds row m = (i & 3) + 8 (i >> 2) + 4 h of it; smaller m = larger d = preferred
-    const int bm = tid & 31;
-    const bool bvalid = (uint32_t)(vb0 + tid - g.st.b_lo) <= (uint32_t)(g.st.b_hi - g.st.b_lo) && g.st.b_hi >= g.st.b_lo;
-    const uint32_t btag = (uint32_t)((bm & 3) + 4 * (bm >> 3)) + (bvalid ? 0u : (uint32_t)kPoison);
-    uint32_t gsum = 0u; // (window sum of b^^2) + 2 E, modulo 2^32
+    // ---- the rows a step touches: ring offsets (bytes) and the byte phases of raw index 0, one scalar each --------
+    // Set once with a modulo, then advanced by one row per step.  Strip row i sits in slot i mod NR of the raw rings
+    // and in slot i mod NRO of the operand ring.
+    const uint32_t cpBase = wave == 0 ? ringA : ringB, cpRB = wave == 0 ? RBA : RBB; // (the copying waves)
+    const int ipx = -WH - g.wy0; // the output row of step s - 1 has its own pixels in strip row s + ipx
+    uint32_t cCp, aIn, aOut, aPx, bSt, oWr, oIn, oOut, oSq, phIn, phOut, phPx, phSt;
+    auto set_cursors = [&](int s) __attribute__((always_inline)) {
+        auto slot = [](int i, int rows) __attribute__((always_inline)) { return (uint32_t)(((i % rows) + rows) % rows); };
+        cCp = slot(s + 3, NR) * cpRB;
+        aIn = slot(s, NR) * RBA, aOut = slot(s - WH, NR) * RBA, aPx = slot(s + ipx, NR) * RBA;
+        bSt = slot(s + 1, NR) * RBB;
+        oWr = slot(s + 1, NRO) * OPROW, oIn = slot(s, NRO) * OPROW, oOut = slot(s - WH, NRO) * OPROW, oSq = slot(s + 1 - WH, NRO) * OPROW;
+        phIn = (phA0 + (uint32_t)s * stA) & 15u, phOut = (phA0 + (uint32_t)(s - WH) * stA) & 15u, phPx = (phA0 + (uint32_t)(s + ipx) * stA) & 15u;
+        phSt = (phB0 + (uint32_t)(s + 1) * stB) & 15u;
+    };
+    auto advance = [&]() __attribute__((always_inline)) {
+        mfma_advance(cCp, cpRB, (uint32_t)NR * cpRB);
+        mfma_advance(aIn, RBA, (uint32_t)NR * RBA), mfma_advance(aOut, RBA, (uint32_t)NR * RBA), mfma_advance(aPx, RBA, (uint32_t)NR * RBA);
+        mfma_advance(bSt, RBB, (uint32_t)NR * RBB);
+        mfma_advance(oWr, OPROW, (uint32_t)NRO * OPROW), mfma_advance(oIn, OPROW, (uint32_t)NRO * OPROW);
+        mfma_advance(oOut, OPROW, (uint32_t)NRO * OPROW), mfma_advance(oSq, OPROW, (uint32_t)NRO * OPROW);
+        phIn = (phIn + stA) & 15u, phOut = (phOut + stA) & 15u, phPx = (phPx + stA) & 15u, phSt = (phSt + stB) & 15u;
+    };
 
-    // ---- the accumulators ---------------------------------------------------------------------------------------
-    // tile t, register i: e = d - d_lo = 32 (NV - 1 - t) + n - m; outside [0, dspan]: poisoned for good
-    ws_i32x16 acc[NVW];
-    uint32_t active = 0u; // this wave's tiles with a valid candidate (a narrow range skips the others' MFMAs)
-#pragma unroll
-    for (int j = 0; j < NVW; ++j) {
-        const int t = wv * NVW + j;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int m = (i & 3) + 8 * (i >> 2) + 4 * h;
-            const int e = 32 * (NV - 1 - t) + n - m;
-            acc[j][i] = (uint32_t)e <= (uint32_t)dspan ? 0 : kPoison >> (KT + 1);
-        }
-        if (t < NV && 32 * (NV - 1 - t) - 31 <= dspan) active |= 1u << j; // (its smallest e is within the range; 31 >= 0 always is)
-    }
-    const uint32_t all_tiles = (1u << min(NVW, NV - wv * NVW)) - 1u; // this wave's share of the tiles
-    const bool wave_on = tile_x0 + 32 * wx < g.ox1; // (a wave all of whose columns lie past the interior only helps with the stages)
+    const bool wave_on = tile_x0 + 32 * wx < g.ox1; // (a wave all of whose columns lie past the interior only helps with the operand pass)
 
-    // pad mask of the A operand: bytes K .. 31 of the 32 a lane pair holds are zero (h = 1 holds bytes 16 .. 31)
+    // pad mask of an operand part: bytes K .. 31 of the 32 a lane pair holds are outside the window (h = 1 holds bytes 16 .. 31)
     ws_i32x4 amask;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -197,123 +232,170 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
         const int keep = K - first;       // bytes of it inside the window
         amask[j] = keep >= 4 ? -1 : keep <= 0 ? 0 : (int)((1u << (8 * keep)) - 1u);
     }
-    const uint32_t pA_lane = 3u * (uint32_t)(32 * wx + n) + 16u * (uint32_t)h; // byte of this lane's operand part in a raw A row
-    const uint32_t opB_lane = 1024u * (uint32_t)(wx + wv * NVW) + 16u * (uint32_t)lane; // ... in an operand row of B, tile j of this wave: + 1024 j
+    const uint32_t pA_lane = ringA + 3u * (uint32_t)(32 * wx + n) + 16u * (uint32_t)h; // byte of this lane's operand part in a raw A row
+    const uint32_t px_lane = ringA + 3u * (uint32_t)(32 * wx + n - g.st.wx0);         // ... of its own pixel
 
     __syncthreads();
 
-    int my_cw = 0, my_G = 0; // the first wave's own best of the last step
-    // the output row of step sp: the better of the two waves' candidates, the fallback, the black-pixel rule
-    auto flush = [&](int sp) __attribute__((always_inline)) {
-        if (wv != 0 || !wave_on) return;
-        const ws_i32x2 o = *reinterpret_cast<const lds_i64 *>((uintptr_t)(mrg + 8u * (uint32_t)((sp & 1) * TX + 32 * wx + n)));
-        int cw = my_cw, G = my_G;
-        if (o.x < cw || (o.x == cw && o.y < G)) { cw = o.x; G = o.y; }
-        const int oi = sp - (WH - 1);
-        const int x = tile_x0 + 32 * wx + n, y = ys + oi;
-        if (h == 0 && x < g.ox1) {
-            float val;
-            if (cw >= (kValidKeyBound >> KT)) val = g.fallback_neg ? -(float)x : (float)x; // no valid candidate
-            else val = (float)(g.d_lo + 32 * (NV - 1) + n - G);
-            // black pixel: image row y is strip row oi - wy0, column x raw index 32 wx + n - wx0 of ring A
-            const int ic = oi - g.wy0;
-            const uint32_t p = phase_a(ic) + 3u * (uint32_t)(32 * wx + n - g.st.wx0);
-            const lds_u32 *q = lds_at32(ringA + slot_of(ic) * RBA + (p & ~3u));
-            const uint32_t px = __builtin_amdgcn_alignbyte(q[1], q[0], p & 3u) & 0x00ffffffu;
-            if (px == kCentre) val = 0.0f;
-            if (g.out16) g.out16[(size_t)y * g.out_pitch + x] = (int16_t)(int)val;
-            else g.out[(size_t)y * g.out_pitch + x] = val;
-        }
+    // tile j of a wave with share v is candidate tile t = v NVW + j; its smallest e = d - d_lo is 32 (NV - 1 - t) - 31
+    auto tiles_active = [&](int v) __attribute__((always_inline)) {
+        uint32_t on = 0u;
+        for (int j = 0; j < (v == 0 ? NVW : NV - NVW); ++j)
+            if (32 * (NV - 1 - (v * NVW + j)) - 31 <= dspan) on |= 1u << j;
+        return on;
     };
 
-    auto step = [&](int s, auto phase) __attribute__((always_inline)) {
-        // PHASE -1: the stages alone, 0: rows enter, 1: the strip's first output row, 2: a row enters, a row leaves
-        constexpr int PHASE = decltype(phase)::value;
-        if constexpr (PHASE == 2) flush(s - 1);
-        // 1. copy row s + 3 (wave 0: image A, wave 1: image B)
-        if (wave < 2 && s + 3 < nsteps) {
-            const uint32_t sl = slot_of(s + 3);
-            raw_dma(wave == 0 ? ringA + sl * RBA : ringB + sl * RBB, dmaMine, s + 3, lane);
+    // ---- a wave's march down the strip; WV: its share of the tiles, and with it its role -------------------------
+    // ALL: every tile of the wave has a candidate inside [d_lo, d_hi] -- the usual case; its tile loop has no branch, so
+    // the compiler overlaps the tiles' operand reads, MFMAs and keys.  A narrow range takes the march that skips tiles.
+    // (One march or the other for the whole strip: a choice per step would meet in copies of every accumulator.)
+    auto march = [&](auto role, auto all) __attribute__((always_inline)) {
+        constexpr int WV = decltype(role)::value;
+        constexpr bool ALL = decltype(all)::value;
+        constexpr int NTL = WV == 0 ? NVW : NV - NVW; // tiles of this wave
+        constexpr int NI = WV == 0 ? 1 : 2;           // blocks of 32 target centres it prepares per step
+        static_assert(kMfmaXWaves * (1 + 2) == (TX + 32 * (NV - 1)) / 32, "the waves' blocks are the tile row's");
+        const uint32_t opB_lane = opB + 1024u * (uint32_t)(wx + WV * NVW) + 16u * (uint32_t)lane; // this wave's operands in an operand row, tile j: + 1024 j
+
+        // ---- the operand pass: block blk0 + k, lane pair (n, n + 32) = target centre vb0 + 32 (blk0 + k) + n --------
+        // tag: register i of a tile holds row m = (i & 3) + 8 (i >> 2) + 4 h of it; smaller m = larger d = preferred
+        const int blk0 = WV == 0 ? wx : kMfmaXWaves + 2 * wx;
+        uint32_t gsum[NI], btag[NI]; // (window sum of b^^2) + 2 E, modulo 2^32; the tie tag and the poison
+#pragma unroll
+        for (int k = 0; k < NI; ++k) {
+            const int v = vb0 + 32 * (blk0 + k) + n;
+            const bool bvalid = (uint32_t)(v - g.st.b_lo) <= (uint32_t)(g.st.b_hi - g.st.b_lo) && g.st.b_hi >= g.st.b_lo;
+            btag[k] = (uint32_t)((n & 3) + 4 * (n >> 3)) + (bvalid ? 0u : (uint32_t)kPoison);
+            gsum[k] = 0u;
         }
-        // 2. row s + 2 landed in the last step: centre its bytes
-        if (s + 2 >= 0 && s + 2 < nsteps) {
-            const uint32_t sl = slot_of(s + 2);
-            const int na16 = (int)(RBA >> 4), nb16 = (int)(RBB >> 4);
-            for (int k = tid; k < na16 + nb16; k += NT) {
-                const uint32_t at = k < na16 ? ringA + sl * RBA + 16u * (uint32_t)k : ringB + sl * RBB + 16u * (uint32_t)(k - na16);
-                uint4 v = lds_load128(at);
-                v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
-                lds_store128(at, v);
+        const uint32_t st_lane = ringB + 3u * (uint32_t)(32 * blk0 + n) + 16u * (uint32_t)h; // this lane's 16 bytes in a raw B row
+        const uint32_t it_lane = opB + 1024u * (uint32_t)blk0 + 16u * (uint32_t)lane;         // ... in an operand row
+        const uint32_t bi_lane = biasr + 4u * (uint32_t)(32 * blk0 + n);
+
+        // ---- the accumulators -----------------------------------------------------------------------------------
+        // tile t, register i: e = d - d_lo = 32 (NV - 1 - t) + n - m; outside [0, dspan]: poisoned for good
+        ws_i32x16 acc[NTL];
+        const uint32_t active = tiles_active(WV); // this wave's tiles with a valid candidate
+#pragma unroll
+        for (int j = 0; j < NTL; ++j) {
+            const int t = WV * NVW + j;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int m = (i & 3) + 8 * (i >> 2) + 4 * h;
+                const int e = 32 * (NV - 1 - t) + n - m;
+                acc[j][i] = (uint32_t)e <= (uint32_t)dspan ? 0 : kPoison >> (KT + 1);
             }
         }
-        // 3. the bias value of this thread's target centre for step s + 1: row s + 1 enters, row s + 1 - WH leaves
-        if (s + 1 >= 0 && s + 1 < nsteps && tid < L.nvc) {
-            const int iu = s + 1;
-            constexpr int NDW = (K + 3) / 4; // dwords that hold a window's K bytes
-            auto window = [&](int i, uint32_t (&d)[NDW]) __attribute__((always_inline)) {
-                const uint32_t p = phase_b(i) + 3u * (uint32_t)tid;
-                const lds_u32 *q = lds_at32(ringB + slot_of(i) * RBB + (p & ~3u));
-                uint32_t r[NDW + 1];
+
+        MfmaRaw ir[NI]; // the entering row's raw bytes
+        uint4 il[NI];   // the leaving row's operand bytes
+        auto items_load = [&](auto leaves) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < NDW + 1; ++j) r[j] = q[j];
+            for (int k = 0; k < NI; ++k) {
+                ir[k] = mfma_raw_load(st_lane + 96u * (uint32_t)k + bSt + phSt);
+                if constexpr (decltype(leaves)::value) il[k] = lds_load128(it_lane + 1024u * (uint32_t)k + oSq);
+            }
+        };
+        // row iu enters the windows of the target centres, row iu - WH leaves them
+        auto items_finish = [&](int iu, auto leaves) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < NDW; ++j) {
-                    d[j] = __builtin_amdgcn_alignbyte(r[j + 1], r[j], p & 3u);
-                    const int keep = K - 4 * j;
-                    if (keep < 4) d[j] &= (1u << (8 * keep)) - 1u; // (the centred bytes past the window count as zeros)
+            for (int k = 0; k < NI; ++k) {
+                ws_i32x4 c = mfma_raw_align(ir[k]);
+                c ^= (int)0x80808080u;
+                lds_store128(it_lane + 1024u * (uint32_t)k + oWr, make_uint4((uint32_t)c.x, (uint32_t)c.y, (uint32_t)c.z, (uint32_t)c.w));
+                const ws_i32x4 cm = c & amask; // (the bytes past the window count as zeros)
+                int q = 0, t = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    q = __builtin_amdgcn_sdot4(c[j], cm[j], q, false);
+                    t = __builtin_amdgcn_sdot4(cm[j], 0x01010101, t, false);
                 }
-            };
-            uint32_t d[NDW];
-            window(iu, d);
+                uint32_t u = (uint32_t)q + 2u * (uint32_t)t;
+                if constexpr (decltype(leaves)::value) {
+                    const ws_i32x4 l = {(int)il[k].x, (int)il[k].y, (int)il[k].z, (int)il[k].w};
+                    const ws_i32x4 lm = l & amask;
+                    int lq = 0;
 #pragma unroll
-            for (int j = 0; j < NDW; ++j) {
-                gsum = (uint32_t)__builtin_amdgcn_sdot4((int)d[j], (int)d[j], (int)gsum, false);
-                gsum += 2u * (uint32_t)__builtin_amdgcn_sdot4((int)d[j], 0x01010101, 0, false);
-            }
-            if (iu >= WH) {
-                window(iu - WH, d);
-                uint32_t lq = 0u;
-#pragma unroll
-                for (int j = 0; j < NDW; ++j) {
-                    lq = (uint32_t)__builtin_amdgcn_sdot4((int)d[j], (int)d[j], (int)lq, false);
+                    for (int j = 0; j < 4; ++j) lq = __builtin_amdgcn_sdot4(l[j], lm[j], lq, false);
+                    u -= (uint32_t)lq;
                 }
-                gsum -= lq;
+                gsum[k] += mfma_pair_sum(u);
+                // (both lanes of a pair write the one word)
+                *reinterpret_cast<lds_u32 *>((uintptr_t)(bi_lane + 4u * (uint32_t)((iu & 1) * L.nvc + 32 * k))) = (gsum[k] << KT) + btag[k];
             }
-            *reinterpret_cast<lds_u32 *>((uintptr_t)(biasr + 4u * (uint32_t)((iu & 1) * L.nvc + tid))) = (gsum << KT) + btag;
-        }
-        // 4. row s + 1 of the target image as MFMA operands: per block of 32 target centres 64 lanes x 16 bytes, lane-linear,
-        //    so that the waves that multiply it -- up to 8 per block, when it enters and again when it leaves -- read one
-        //    aligned ds_read_b128 each instead of assembling it from the raw bytes
-        if (s + 1 >= 0 && s + 1 < nsteps) {
-            const uint32_t rowB = ringB + slot_of(s + 1) * RBB, dst = opB + opslot_of(s + 1) * OPROW, phb = phase_b(s + 1);
-            for (int k = tid; k < 64 * L.nblk; k += NT) { // (whole waves: k >> 6 is the block)
-                const ws_i32x4 v = mfma_operand(rowB, phb + 3u * (uint32_t)(32 * (k >> 6) + n) + 16u * (uint32_t)h);
-                lds_store128(dst + 16u * (uint32_t)k, make_uint4((uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w));
+        };
+
+        // ---- the output row of step sp: the better of the two waves' candidates, the fallback, the black-pixel rule ----
+        int my_cw = 0, my_G = 0; // this wave's own best of the last step
+        struct Flush {
+            ws_i32x2 o;
+            uint32_t q0, q1, sh;
+        };
+        auto flush_load = [&](int sp) __attribute__((always_inline)) {
+            Flush f;
+            f.o = *reinterpret_cast<const lds_i64 *>((uintptr_t)(mrg + 8u * (uint32_t)((sp & 1) * TX + 32 * wx + n)));
+            // black pixel: the output pixel's own bytes, raw, in ring A
+            const uint32_t p = px_lane + aPx + phPx;
+            const lds_u32 *q = lds_at32(p & ~3u);
+            f.q0 = q[0], f.q1 = q[1], f.sh = p & 3u;
+            return f;
+        };
+        auto flush_store = [&](int sp, const Flush &f) __attribute__((always_inline)) {
+            int cw = my_cw, G = my_G;
+            if (f.o.x < cw || (f.o.x == cw && f.o.y < G)) { cw = f.o.x; G = f.o.y; }
+            const int x = tile_x0 + 32 * wx + n, y = ys + sp - (WH - 1);
+            if (h == 0 && x < g.ox1) {
+                float val;
+                if (cw >= (kValidKeyBound >> KT)) val = g.fallback_neg ? -(float)x : (float)x; // no valid candidate
+                else val = (float)(g.d_lo + 32 * (NV - 1) + n - G);
+                if ((__builtin_amdgcn_alignbyte(f.q1, f.q0, f.sh) & 0x00ffffffu) == 0u) val = 0.0f;
+                if (g.out16) g.out16[(size_t)y * g.out_pitch + x] = (int16_t)(int)val;
+                else g.out[(size_t)y * g.out_pitch + x] = val;
             }
-        }
-        // 5. the matrix cores: row s enters every window, row s - WH leaves it; keys and the output row
-        if constexpr (PHASE >= 0) {
-            if (wave_on) {
-                const uint32_t rowAe = ringA + slot_of(s) * RBA, rowAl = ringA + slot_of(s - WH) * RBA;
-                const uint32_t pae = phase_a(s) + pA_lane, pal = phase_a(s - WH) + pA_lane;
-                const uint32_t opBe = opB + opslot_of(s) * OPROW + opB_lane, opBl = opB + opslot_of(s - WH) * OPROW + opB_lane;
-                ws_i32x4 ae = mfma_operand(rowAe, pae), al;
-                ae = ~ae & amask; // (the complement first, then the pad: it must stay zero)
-                if constexpr (PHASE == 2) al = mfma_operand(rowAl, pal) & amask;
+        };
+
+        auto step = [&](int s, auto phase) __attribute__((always_inline)) {
+            // PHASE -1: the stages alone, 0: rows enter, 1: the strip's first output row, 2: a row enters, a row leaves
+            // (the steady phase: every stage has its row), 3: the same with the strip's end in sight
+            constexpr int PHASE = decltype(phase)::value;
+            constexpr bool STEADY = PHASE == 2;
+            using Leaves = std::integral_constant<bool, (PHASE >= 1)>; // row s + 1 - WH exists
+            Flush fl{};
+            if constexpr (WV == 1 && PHASE >= 2) {
+                if (wave_on) fl = flush_load(s - 1);
+            }
+            // the copy of row s + 3 (wave 0: image A, wave 1: image B)
+            if constexpr (WV == 0) {
+                if (wave < 2 && (STEADY || s + 3 < nsteps)) raw_dma(cpBase + cCp, dmaMine, s + 3, lane);
+            }
+            // row s + 1 of the target image: the lane-linear MFMA operands of its blocks, so that the waves that multiply
+            // a block -- up to 8, when the row enters and again when it leaves -- read one aligned ds_read_b128 each, and
+            // the bias' values of step s + 1
+            const bool stage = STEADY || (s + 1 >= 0 && s + 1 < nsteps);
+            if constexpr (STEADY) items_load(Leaves());
+            // the matrix cores: row s enters every window, row s - WH leaves it; keys and the output row
+            if (PHASE >= 0 && wave_on) {
+                const MfmaRaw rae = mfma_raw_load(pA_lane + aIn + phIn);
+                MfmaRaw ral{};
+                if constexpr (PHASE >= 2) ral = mfma_raw_load(pA_lane + aOut + phOut);
+                const uint32_t opBe = opB_lane + oIn, opBl = opB_lane + oOut;
+                if constexpr (STEADY) items_finish(s + 1, Leaves());
+                else if (stage) { items_load(Leaves()); items_finish(s + 1, Leaves()); }
+                // -a^ - 1 = a xor 0x7f, a^ = a xor 0x80; the pad must stay zero
+                const ws_i32x4 ae = (mfma_raw_align(rae) ^ (int)0x7f7f7f7fu) & amask;
+                ws_i32x4 al{};
+                if constexpr (PHASE >= 2) al = (mfma_raw_align(ral) ^ (int)0x80808080u) & amask;
                 int bestk = INT_MAX, bestt = 0;
-                const uint32_t brow = biasr + 4u * (uint32_t)((s & 1) * L.nvc + 32 * (wx + wv * NVW) + 4 * h);
-                // (all of a wave's tiles active -- the usual case -- is a loop without branches: the compiler then overlaps
-                // the tiles' operand reads, MFMAs and keys; a narrow range takes the loop that skips tiles)
-                auto tiles = [&](auto all) __attribute__((always_inline)) {
+                const uint32_t brow = biasr + 4u * (uint32_t)((s & 1) * L.nvc + 32 * (wx + WV * NVW) + 4 * h);
 #pragma unroll
-                for (int t = 0; t < NVW; ++t) { // (t: the tile's index in this wave)
-                    if constexpr (!decltype(all)::value || (NV % NVW != 0)) { // (the second wave's share is one tile short)
-                        if ((!decltype(all)::value || t == NVW - 1) && !(active & (1u << t))) continue; // (uniform)
+                for (int t = 0; t < NTL; ++t) { // (t: the tile's index in this wave)
+                    if constexpr (!ALL) {
+                        if (!(active & (1u << t))) continue; // (uniform)
                     }
                     const uint4 be4 = lds_load128(opBe + 1024u * (uint32_t)t);
                     const ws_i32x4 be = {(int)be4.x, (int)be4.y, (int)be4.z, (int)be4.w};
                     acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(be, ae, acc[t], 0, 0, 0);
-                    if constexpr (PHASE == 2) {
+                    if constexpr (PHASE >= 2) {
                         const uint4 bl4 = lds_load128(opBl + 1024u * (uint32_t)t);
                         const ws_i32x4 bl = {(int)bl4.x, (int)bl4.y, (int)bl4.z, (int)bl4.w};
                         acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bl, al, acc[t], 0, 0, 0);
@@ -337,39 +419,57 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                         bestt = better ? t : bestt;
                     }
                 }
-                };
-                if (active == all_tiles) tiles(std::true_type());
-                else tiles(std::false_type());
                 if constexpr (PHASE >= 1) {
                     // the two halves of a column: G = 32 t + m orders ALL its candidates (smaller = larger d)
                     const int i_best = bestk & ((1 << KT) - 1);
-                    int G = 32 * (bestt + wv * NVW) + (i_best & 3) + 8 * (i_best >> 2) + 4 * h;
+                    int G = 32 * (bestt + WV * NVW) + (i_best & 3) + 8 * (i_best >> 2) + 4 * h;
                     int cw = bestk >> KT; // the cost word
                     const int cw_o = __shfl_xor(cw, 32, 64), G_o = __shfl_xor(G, 32, 64);
                     if (cw_o < cw || (cw_o == cw && G_o < G)) { cw = cw_o; G = G_o; }
-                    // the second wave of a column leaves its best in LDS for the first, which writes the row out in the next step
-                    if (wv == 1) {
-                        if (h == 0) *reinterpret_cast<lds_i64 *>((uintptr_t)(mrg + 8u * (uint32_t)((s & 1) * TX + 32 * wx + n))) = ws_i32x2{cw, G};
+                    if constexpr (WV == 1 && PHASE >= 2) flush_store(s - 1, fl);
+                    // the first wave of a column leaves its best in LDS for the second, which writes the row out in the
+                    // next step (both lanes of a column write the one pair)
+                    if constexpr (WV == 0) {
+                        *reinterpret_cast<lds_i64 *>((uintptr_t)(mrg + 8u * (uint32_t)((s & 1) * TX + 32 * wx + n))) = ws_i32x2{cw, G};
                     } else {
                         my_cw = cw;
                         my_G = G;
                     }
                 }
+            } else {
+                if constexpr (STEADY) items_finish(s + 1, Leaves());
+                else if (stage) { items_load(Leaves()); items_finish(s + 1, Leaves()); }
             }
-        }
-        if (wave < 2) dma_wait();
-        __syncthreads();
-    };
+            if constexpr (WV == 0) {
+                if (wave < 2) dma_wait(); // (the copy lands inside its step: a wait that lets it span the barrier measured slower)
+            }
+            __syncthreads();
+            advance();
+        };
 
-    int s = -3;
+        int s = -3;
+        set_cursors(s);
 #pragma unroll 1
-    for (; s < 0; ++s) step(s, std::integral_constant<int, -1>());
+        for (; s < 0; ++s) step(s, std::integral_constant<int, -1>());
 #pragma unroll 1
-    for (; s < WH - 1; ++s) step(s, std::integral_constant<int, 0>());
-    step(s++, std::integral_constant<int, 1>());
+        for (; s < WH - 1; ++s) step(s, std::integral_constant<int, 0>());
+        step(s++, std::integral_constant<int, 1>());
 #pragma unroll 1
-    for (; s < nsteps; ++s) step(s, std::integral_constant<int, 2>());
-    flush(nsteps - 1); // the last row
+        for (; s + 3 < nsteps; ++s) step(s, std::integral_constant<int, 2>());
+#pragma unroll 1
+        for (; s < nsteps; ++s) step(s, std::integral_constant<int, 3>());
+        if constexpr (WV == 1) {
+            if (wave_on) flush_store(nsteps - 1, flush_load(nsteps - 1)); // the last row
+        }
+    };
+    const bool all = tiles_active(wv) == (1u << (wv == 0 ? NVW : NV - NVW)) - 1u;
+    if (wv == 0) {
+        if (all) march(std::integral_constant<int, 0>(), std::true_type());
+        else march(std::integral_constant<int, 0>(), std::false_type());
+    } else {
+        if (all) march(std::integral_constant<int, 1>(), std::true_type());
+        else march(std::integral_constant<int, 1>(), std::false_type());
+    }
 }
 
 } // namespace wsamd
