@@ -340,6 +340,59 @@ int ws_search_sgm_device(ws_context *ctx, const ws_params *p, const ws_sgm_param
 int ws_search_sgm_host(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *left,
                        const ws_image *right, void *out, int out_stride, int out_dtype);
 
+/* ---- uniqueness ratio and confidence (extension) --------------------------------------------- */
+/*
+ * OpenCV's uniquenessRatio for the block search and for SGM: a pixel whose best cost is not clearly better than its best
+ * rival is dropped, and the margin itself is available as a confidence plane.  p, the views, K(p), C(p, j), nodes and
+ * the fallbacks are those of the SGM section (j = the index of a disparity in the view's range).  S(p, j) depends on
+ * `sgm`: non-null, it is that section's sum over the paths; NULL, S = C: the block search at smoothFactor 1 (no path
+ * kernel runs and no sum plane is allocated).
+ *   1. Winner: jb = argmin of S over K(p) with the view's tie rule (unchanged), Smin = S(p, jb).
+ *   2. Rivals: the j in K(p) with |j - jb| >= 2; m2 = the minimum of S over them.  A node without rivals is uncontested:
+ *      K(p) is an interval, so these are the nodes with at most 2 candidates and those with 3 whose winner is the
+ *      middle one.
+ *   3. Fail test: a contested node fails iff m2 * (100 - ratio) < Smin * 100, in exact integers.  This is StereoSGBM's
+ *      test, strict `<` included: an exact tie with Smin == 0 (then m2 == 0 too) passes at every ratio.  ratio == 0 fails
+ *      nothing; ratio == 100 fails every contested node with Smin > 0.
+ *   4. Map: a failed node stores 0.0f ("no disparity", as after the left-right check); a passing node stores exactly what
+ *      ws_search_sgm_* stores (sgm == NULL: what ws_search_* stores), the sub-pixel value included; non-nodes are
+ *      unchanged (x / -x / 0).
+ *   5. Confidence, an optional float32 plane that does not depend on ratio: a contested node with m2 > 0 stores
+ *      (float)((double)(m2 - Smin) / (double)m2); a contested node with m2 == 0 stores 0.0f; an uncontested node 1.0f;
+ *      a non-node 0.0f.
+ *   6. Counts: {failed nodes, nodes} of the last call.
+ *   7. Identities: (a) with ratio == 0 the map is ws_search_sgm_*'s (sgm == NULL: ws_search_*'s) bit for bit; (b)
+ *      sgm == NULL and sgm = {paths, 0, 0} give the same map and the same confidence (S = paths * C scales both sides of
+ *      rule 3 and cancels in rule 5); (c) the fail set grows with ratio.
+ *   8. Refusals, without a device: everything ws_validate_sgm refuses (sgm == NULL: the same list without the checks of
+ *      sgm itself); WS_ERR_ARG for a null ws_unique_params, ratio outside 0 .. 100, conf_stride < width for a given
+ *      confidence plane, or a confidence plane that overlaps the map.
+ * The scratch is the SGM calls' own (sgm == NULL: the intervals and C only), so a uniqueness call and an SGM call on two
+ * streams order themselves as two SGM calls do.  A map feeds ws_lr_check_device, ws_filter_speckles_device and the
+ * consumers as it is (ws_convert_disparity_to_depth: 0 -> -inf, the mesh leaves the vertex out).
+ */
+typedef struct {
+    int ratio; /* 0 .. 100, OpenCV's uniquenessRatio: the margin in percent by which the best cost must win */
+} ws_unique_params;
+
+/* The argument checks of the uniqueness calls without a device; sgm may be NULL. */
+int ws_validate_unique(const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq, const ws_image *left,
+                       const ws_image *right);
+/* Host only: the device memory such a call would hold (sgm == NULL: ws_sgm_scratch_bytes without the sum plane). */
+int ws_unique_scratch_bytes(const ws_params *p, const ws_sgm_params *sgm, const ws_image *left, const ws_image *right,
+                            unsigned long long *bytes);
+/* On device images into a float32 device map and, if conf_dev is not NULL, a float32 confidence plane (strides in
+ * floats).  Only enqueues, on `stream` (NULL = the context's own). */
+int ws_search_unique_device(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq,
+                            const ws_image *left_dev, const ws_image *right_dev, float *out_dev, int out_stride, float *conf_dev,
+                            int conf_stride, void *stream);
+/* On host buffers, synchronous, as ws_search_sgm_host; conf (float32, conf_stride floats per row) may be NULL. */
+int ws_search_unique_host(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq,
+                          const ws_image *left, const ws_image *right, void *out, int out_stride, int out_dtype, float *conf,
+                          int conf_stride);
+/* {failed nodes, nodes} of the last uniqueness call of this context; waits for that call's stream. */
+int ws_last_unique_counts(ws_context *ctx, unsigned long long counts[2]);
+
 /* ---- census-transform matching cost (extension) -------------------------------------------- */
 /*
  * WS_COST_CENSUS_5X5 / WS_COST_CENSUS_9X7 as ws_params.cost: the block search, and semi-global matching over it, on a

@@ -51,6 +51,8 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_batch_search_host", "ws_lr_check_device", "ws_search_lr_host", "ws_search_lr_device", "ws_last_lr_counts",
            "ws_filter_speckles_device", "ws_filter_speckles_host", "ws_last_speckle_counts",
            "ws_validate_sgm", "ws_sgm_scratch_bytes", "ws_search_sgm_device", "ws_search_sgm_host",
+           "ws_validate_unique", "ws_unique_scratch_bytes", "ws_search_unique_device", "ws_search_unique_host",
+           "ws_last_unique_counts",
            "ws_census_transform_device", "ws_census_transform_host"]
 JOB_NOT_RUN = 1  # ws_job.status of a job its worker never reached (WS_JOB_NOT_RUN)
 
@@ -137,6 +139,46 @@ def sgm_scratch_bytes(params, left, right, paths=8, p1=0, p2=0):
     n = ctypes.c_ulonglong()
     rc = lib.ws_sgm_scratch_bytes(ctypes.byref(params), ctypes.byref(sp), ctypes.byref(_image_struct(left)),
                                   ctypes.byref(_image_struct(right)), ctypes.byref(n))
+    if rc != 0:
+        raise WsError(rc, lib.ws_last_error(None).decode())
+    return int(n.value)
+
+
+class _UniqueParams(ctypes.Structure):
+    _fields_ = [("ratio", ctypes.c_int)]
+
+
+def unique_params(ratio=0):
+    """ws_unique_params: OpenCV's uniquenessRatio, 0 .. 100 (rules in include/ws_stereo.h)."""
+    return _UniqueParams(ratio)
+
+
+def _sgm_or_null(sgm):
+    """sgm: None (the block route), a (paths, p1, p2) tuple or a ws_sgm_params -> (the struct kept alive, its pointer)."""
+    if sgm is None:
+        return None, None
+    sp = sgm if isinstance(sgm, _SgmParams) else sgm_params(*sgm)
+    return sp, ctypes.byref(sp)
+
+
+def validate_unique(params, left, right, ratio=0, sgm=None):
+    """ws_validate_unique on host images: 0 or the WS_ERR_* status a uniqueness call would return.  ratio None: a null
+    ws_unique_params."""
+    lib = load_library()
+    sp, spp = _sgm_or_null(sgm)
+    uq = None if ratio is None else unique_params(ratio)
+    return int(lib.ws_validate_unique(ctypes.byref(params), spp, None if uq is None else ctypes.byref(uq),
+                                      ctypes.byref(_image_struct(left)), ctypes.byref(_image_struct(right))))
+
+
+def unique_scratch_bytes(params, left, right, sgm=None):
+    """ws_unique_scratch_bytes: the device memory a uniqueness call on these images would hold (raises WsError if
+    refused).  sgm None: the intervals and the cost plane only."""
+    lib = load_library()
+    sp, spp = _sgm_or_null(sgm)
+    n = ctypes.c_ulonglong()
+    rc = lib.ws_unique_scratch_bytes(ctypes.byref(params), spp, ctypes.byref(_image_struct(left)),
+                                     ctypes.byref(_image_struct(right)), ctypes.byref(n))
     if rc != 0:
         raise WsError(rc, lib.ws_last_error(None).decode())
     return int(n.value)
@@ -267,6 +309,13 @@ def load_library(build_if_missing=False):
     lib.ws_sgm_scratch_bytes.argtypes = [P(_Params), P(_SgmParams), P(_Image), P(_Image), P(ctypes.c_ulonglong)]
     lib.ws_search_sgm_device.argtypes = [vp, P(_Params), P(_SgmParams), P(_Image), P(_Image), vp, ci, vp]
     lib.ws_search_sgm_host.argtypes = [vp, P(_Params), P(_SgmParams), P(_Image), P(_Image), vp, ci, ci]
+    lib.ws_validate_unique.argtypes = [P(_Params), P(_SgmParams), P(_UniqueParams), P(_Image), P(_Image)]
+    lib.ws_unique_scratch_bytes.argtypes = [P(_Params), P(_SgmParams), P(_Image), P(_Image), P(ctypes.c_ulonglong)]
+    lib.ws_search_unique_device.argtypes = [vp, P(_Params), P(_SgmParams), P(_UniqueParams), P(_Image), P(_Image), vp, ci,
+                                            vp, ci, vp]
+    lib.ws_search_unique_host.argtypes = [vp, P(_Params), P(_SgmParams), P(_UniqueParams), P(_Image), P(_Image), vp, ci, ci,
+                                          vp, ci]
+    lib.ws_last_unique_counts.argtypes = [vp, P(ctypes.c_ulonglong)]
     lib.ws_census_transform_device.argtypes = [vp, P(_Image), ci, vp, ci, vp]
     lib.ws_census_transform_host.argtypes = [vp, P(_Image), ci, vp, ci]
     _lib = lib
@@ -453,6 +502,53 @@ class WindowSearch:
         self._check(self._lib.ws_search_sgm_device(self._h, ctypes.byref(params), ctypes.byref(sp), ctypes.byref(Li),
                                                    ctypes.byref(Ri), out_t.data_ptr(), out_t.stride(0),
                                                    ctypes.c_void_p(stream or 0)))
+
+    # -- uniqueness ratio and confidence (extension; rules in include/ws_stereo.h) ----------------
+    def search_unique(self, params, left, right, ratio, sgm=None, dtype=np.float64, out=None, conf=False):
+        """ws_search_unique_host: the view's map with the nodes that fail the uniqueness test at `ratio` set to 0.  sgm:
+        None for the block search's costs, or (paths, p1, p2) for semi-global matching.  `out` as for search().  conf:
+        True returns (map, confidence) with a fresh float32 plane; a C-contiguous float32 array of the map's shape is
+        written into and returned the same way."""
+        La, Li = _host_image(left)
+        Ra, Ri = _host_image(right)
+        shape = La.shape[:2] if params.view == VIEW_LEFT else Ra.shape[:2]
+        if out is None:
+            out = np.empty(shape, dtype=dtype)
+        elif out.shape != shape or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("out must be a C-contiguous array of shape %s" % (shape,))
+        if out.dtype not in (np.float32, np.float64):
+            raise ValueError("dtype must be float32 or float64")
+        if conf is True:
+            conf = np.empty(shape, dtype=np.float32)
+        elif conf is False or conf is None:
+            conf = None
+        elif conf.shape != shape or conf.dtype != np.float32 or not conf.flags["C_CONTIGUOUS"]:
+            raise ValueError("conf must be a C-contiguous float32 array of shape %s" % (shape,))
+        sp, spp = _sgm_or_null(sgm)
+        uq = unique_params(ratio)
+        self._check(self._lib.ws_search_unique_host(self._h, ctypes.byref(params), spp, ctypes.byref(uq), ctypes.byref(Li),
+                                                    ctypes.byref(Ri), out.ctypes.data, shape[1],
+                                                    OUT_F64 if out.dtype == np.float64 else OUT_F32,
+                                                    None if conf is None else conf.ctypes.data, shape[1]))
+        return out if conf is None else (out, conf)
+
+    def search_unique_device(self, params, left_t, right_t, out_t, ratio, sgm=None, conf_t=None, stream=None):
+        """ws_search_unique_device on uint8 CUDA images, a float32 CUDA map and, if given, a float32 CUDA confidence
+        plane (rows may be padded).  Only enqueues."""
+        Li = _Image(left_t.data_ptr(), left_t.shape[1], left_t.shape[0], left_t.stride(0))
+        Ri = _Image(right_t.data_ptr(), right_t.shape[1], right_t.shape[0], right_t.stride(0))
+        sp, spp = _sgm_or_null(sgm)
+        uq = unique_params(ratio)
+        self._check(self._lib.ws_search_unique_device(
+            self._h, ctypes.byref(params), spp, ctypes.byref(uq), ctypes.byref(Li), ctypes.byref(Ri), out_t.data_ptr(),
+            out_t.stride(0), None if conf_t is None else conf_t.data_ptr(), 0 if conf_t is None else conf_t.stride(0),
+            ctypes.c_void_p(stream or 0)))
+
+    def last_unique_counts(self):
+        """ws_last_unique_counts: (failed nodes, nodes) of the last uniqueness call of this context."""
+        c = (ctypes.c_ulonglong * 2)()
+        self._check(self._lib.ws_last_unique_counts(self._h, c))
+        return int(c[0]), int(c[1])
 
     # -- census transform (extension; rules in include/ws_stereo.h) -------------------------------
     def census_transform(self, img, cost):

@@ -55,9 +55,13 @@ struct SpeckleState {
 
 // Semi-global matching's device memory (ws_sgm.cpp): the candidate intervals, the cost plane and the path sums of one
 // call, grown to what the call needs.  Shared by every SGM call of the context, with the same cross-stream wait as
-// LrState; the searches' own scratch (Searcher) is apart from it.
+// LrState; the searches' own scratch (Searcher) is apart from it.  The uniqueness calls (ws_search_unique_*) are SGM
+// calls in this respect: the same scratch, the same event, and their two counters beside it.
 struct SgmState {
     DevBuf scratch;
+    DevBuf counts;           // ws_search_unique_*: {failed nodes, nodes}, zeroed on the stream before the winner kernel
+    HostBuf counts_host;     // ... copied here behind it
+    bool unique_ran = false; // such a call was enqueued: counts_host holds (or will hold) its counts
     hipEvent_t ev = nullptr; // end of the last SGM call
     hipStream_t stream = nullptr;
     bool busy = false; // ev is recorded on `stream`

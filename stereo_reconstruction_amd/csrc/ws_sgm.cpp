@@ -1,6 +1,7 @@
 // ws_sgm.cpp -- semi-global matching of include/ws_stereo.h (extension): argument checks, the storage widths from the
 // host's bound, the context's scratch for it (SgmState), and the launches of ws_sgm.hip on device memory or on the
-// caller's host buffers (through ws_staging.h).
+// caller's host buffers (through ws_staging.h).  Also the uniqueness ratio and confidence calls (ws_search_unique_*):
+// the same volumes with another winner kernel, on S or -- without a ws_sgm_params -- on the window costs themselves.
 #include "ws_context.h"
 #include "ws_ct.h"
 #include "ws_sgm.h"
@@ -26,16 +27,20 @@ void disparity_range(const ws_params *p, const ws_image *L, int *d0, int *nd)
     }
 }
 
-int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R)
+// sgm_optional: the uniqueness calls, where a null sgm is the block route and only a given one is checked.
+int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R,
+              bool sgm_optional = false)
 {
     if (const int rc = check_params(err, p, L, R); rc != WS_OK) return rc;
     if (p->view == WS_VIEW_LINEAR) return fail(err, WS_ERR_UNSUPPORTED, "SGM on LinearSearch");
     if (p->smooth_factor != 1.0) return fail(err, WS_ERR_UNSUPPORTED, "SGM together with smoothFactor != 1");
     if (p->view == WS_VIEW_RIGHT && p->var_block) return fail(err, WS_ERR_UNSUPPORTED, "SGM together with varBlock");
-    if (!sgm) return fail(err, WS_ERR_ARG, "null ws_sgm_params");
-    if (sgm->paths != 4 && sgm->paths != 8) return fail(err, WS_ERR_ARG, "paths %d: must be 4 or 8", sgm->paths);
-    if (sgm->p1 < 0) return fail(err, WS_ERR_ARG, "p1 %d: must be >= 0", sgm->p1);
-    if (sgm->p2 < sgm->p1) return fail(err, WS_ERR_ARG, "p2 %d: must be >= p1 (%d)", sgm->p2, sgm->p1);
+    if (!sgm && !sgm_optional) return fail(err, WS_ERR_ARG, "null ws_sgm_params");
+    if (sgm) {
+        if (sgm->paths != 4 && sgm->paths != 8) return fail(err, WS_ERR_ARG, "paths %d: must be 4 or 8", sgm->paths);
+        if (sgm->p1 < 0) return fail(err, WS_ERR_ARG, "p1 %d: must be >= 0", sgm->p1);
+        if (sgm->p2 < sgm->p1) return fail(err, WS_ERR_ARG, "p2 %d: must be >= p1 (%d)", sgm->p2, sgm->p1);
+    }
     int d0, nd;
     disparity_range(p, L, &d0, &nd);
     if (nd > kSgmMaxNd) return fail(err, WS_ERR_UNSUPPORTED, "SGM over %d disparities: at most %d", nd, kSgmMaxNd);
@@ -44,7 +49,24 @@ int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, co
     return WS_OK;
 }
 
-// The scratch of one call: the candidate intervals, the cost plane and the sums, each 256-byte aligned.  Storage
+// Do two planes of `rows` rows (pitch and row length in bytes) share a byte of their extents?
+bool planes_overlap(const void *a, size_t a_pitch, size_t a_row, const void *b, size_t b_pitch, size_t b_row, size_t rows)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_pitch * (rows - 1) + a_row, b0 = (uintptr_t)b, b1 = b0 + b_pitch * (rows - 1) + b_row;
+    return a0 < b1 && b0 < a1;
+}
+
+int check_unique(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq, const ws_image *L,
+                 const ws_image *R)
+{
+    if (const int rc = check_sgm(err, p, sgm, L, R, true); rc != WS_OK) return rc;
+    if (!uq) return fail(err, WS_ERR_ARG, "null ws_unique_params");
+    if (uq->ratio < 0 || uq->ratio > 100) return fail(err, WS_ERR_ARG, "ratio %d: must be 0 .. 100", uq->ratio);
+    return WS_OK;
+}
+
+// The scratch of one call: the candidate intervals, the cost plane and the sums (none without sgm: the uniqueness calls'
+// block route), each 256-byte aligned.  Storage
 // widths from the bound: C <= Cmax = 3 (255 or 255^2) bs^2 < 2^30 (a census cost: 24 or 62 bs^2); Lr <= C + P2 < 2^32; S <= paths (Cmax + P2).
 struct Layout {
     int d0 = 0, nd = 0, w = 0, h = 0, cost16 = 0, sum64 = 0;
@@ -59,12 +81,12 @@ Layout layout(const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, c
     y.h = p->view == WS_VIEW_LEFT ? L->height : R->height;
     const uint64_t cmax = sgm_cost_max(p->cost, p->block_size);
     y.cost16 = cmax <= 0xffffu;
-    y.sum64 = (uint64_t)sgm->paths * (cmax + (uint64_t)sgm->p2) > 0xffffffffull;
+    y.sum64 = sgm && (uint64_t)sgm->paths * (cmax + (uint64_t)sgm->p2) > 0xffffffffull;
     const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
     const size_t px = (size_t)y.w * y.h, vol = px * (size_t)y.nd;
     y.off_cost = up(px * 4);
     y.off_sum = y.off_cost + up(vol * (y.cost16 ? 2 : 4));
-    y.bytes = y.off_sum + up(vol * (y.sum64 ? 8 : 4));
+    y.bytes = y.off_sum + (sgm ? up(vol * (y.sum64 ? 8 : 4)) : 0);
     if (is_census(p->cost)) {
         const size_t esz = census_plane_elem(p->cost);
         y.off_tl = y.bytes;
@@ -116,9 +138,10 @@ int sgm_release(ws_context *ctx, hipStream_t s)
     return WS_OK;
 }
 
-// Scratch, then the kernels on s into out (out_stride floats per row).
+// Scratch, then the kernels on s into out (out_stride floats per row).  uq: the uniqueness winner instead (sgm may then
+// be null), with the confidence plane conf (or null) and the counts on their way to the host.
 int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
-                int out_stride, hipStream_t s)
+                int out_stride, hipStream_t s, const ws_unique_params *uq = nullptr, float *conf = nullptr, int conf_stride = 0)
 {
     const Layout y = layout(p, sgm, L, R);
     int rc;
@@ -134,11 +157,11 @@ int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, c
     a.half = (p->block_size - 1) / 2;
     a.d0 = y.d0; a.nd = y.nd;
     a.w = y.w; a.h = y.h;
-    a.p1 = (uint32_t)sgm->p1; a.p2 = (uint32_t)sgm->p2;
+    if (sgm) { a.p1 = (uint32_t)sgm->p1; a.p2 = (uint32_t)sgm->p2; }
     auto *base = static_cast<uint8_t *>(ctx->sgm.scratch.p);
     a.kr = reinterpret_cast<uint32_t *>(base);
     a.cost = base + y.off_cost;
-    a.sum = base + y.off_sum;
+    a.sum = sgm ? base + y.off_sum : nullptr;
     a.cost16 = y.cost16; a.sum64 = y.sum64;
     if (is_census(p->cost)) {
         a.TL = base + y.off_tl;
@@ -150,7 +173,23 @@ int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, c
     a.subpixel = p->subpixel != 0;
     a.out = out;
     a.out_pitch = out_stride;
-    WS_HIP(&ctx->err, launch_sgm(a, sgm->paths, s));
+    if (uq) {
+        SgmState &S = ctx->sgm;
+        if ((rc = ensure(&ctx->err, S.counts, 2 * sizeof(unsigned long long))) != WS_OK) return rc;
+        WS_HIP(&ctx->err, host_ensure(S.counts_host, 2 * sizeof(unsigned long long)));
+        UniqueArgs u{};
+        u.ratio = uq->ratio;
+        u.conf = conf;
+        u.conf_pitch = conf_stride;
+        u.counts = static_cast<unsigned long long *>(S.counts.p);
+        u.num_cus = ctx->num_cus;
+        WS_HIP(&ctx->err, hipMemsetAsync(u.counts, 0, 2 * sizeof(unsigned long long), s));
+        WS_HIP(&ctx->err, launch_unique(a, u, sgm ? sgm->paths : 0, s));
+        WS_HIP(&ctx->err, hipMemcpyAsync(S.counts_host.p, u.counts, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        S.unique_ran = true;
+    } else {
+        WS_HIP(&ctx->err, launch_sgm(a, sgm->paths, s));
+    }
     return sgm_release(ctx, s);
 }
 
@@ -220,6 +259,99 @@ int ws_search_sgm_host(ws_context *ctx, const ws_params *p, const ws_sgm_params 
     for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
     ctx->last_wire = kWireF32;
     return finish_host_call(ctx, rc, sp, 3, {s}, "SGM host call");
+}
+
+int ws_validate_unique(const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq, const ws_image *left,
+                       const ws_image *right)
+{
+    return check_unique(nullptr, p, sgm, uq, left, right);
+}
+
+int ws_unique_scratch_bytes(const ws_params *p, const ws_sgm_params *sgm, const ws_image *left, const ws_image *right,
+                            unsigned long long *bytes)
+{
+    if (!bytes) return fail(nullptr, WS_ERR_ARG, "null bytes");
+    if (const int rc = check_sgm(nullptr, p, sgm, left, right, true); rc != WS_OK) return rc;
+    *bytes = layout(p, sgm, left, right).bytes;
+    return WS_OK;
+}
+
+int ws_search_unique_device(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq,
+                            const ws_image *left_dev, const ws_image *right_dev, float *out_dev, int out_stride, float *conf_dev,
+                            int conf_stride, void *stream)
+{
+    // (the refusals come before the context is looked at: they are the rules', and need no device)
+    std::string *err = ctx ? &ctx->err : nullptr;
+    int rc = check_unique(err, p, sgm, uq, left_dev, right_dev);
+    if (rc != WS_OK) return rc;
+    const bool left = p->view == WS_VIEW_LEFT;
+    const int ow = left ? left_dev->width : right_dev->width, oh = left ? left_dev->height : right_dev->height;
+    if (!out_dev) return fail(err, WS_ERR_ARG, "null output");
+    if (out_stride < ow) return fail(err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
+    if (conf_dev) {
+        if (conf_stride < ow) return fail(err, WS_ERR_ARG, "conf_stride %d < width %d", conf_stride, ow);
+        if (planes_overlap(out_dev, (size_t)out_stride * 4, (size_t)ow * 4, conf_dev, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh))
+            return fail(err, WS_ERR_ARG, "the confidence plane overlaps the map");
+    }
+    if (!ctx) return fail(nullptr, WS_ERR_ARG, "null context");
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    return enqueue_sgm(ctx, p, sgm, left_dev, right_dev, out_dev, out_stride, s, uq, conf_dev, conf_stride);
+}
+
+// As ws_search_sgm_host; the confidence plane, when asked for, beside the map in d_out and down as float32.
+int ws_search_unique_host(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq,
+                          const ws_image *left, const ws_image *right, void *out, int out_stride, int out_dtype, float *conf,
+                          int conf_stride)
+{
+    std::string *err = ctx ? &ctx->err : nullptr;
+    int ow, oh;
+    int rc = check_unique(err, p, sgm, uq, left, right);
+    if (rc == WS_OK) rc = check_out(err, p, left, right, out, out_stride, out_dtype, &ow, &oh);
+    if (rc != WS_OK) return rc;
+    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    if (conf) {
+        if (conf_stride < ow) return fail(err, WS_ERR_ARG, "conf_stride %d < width %d", conf_stride, ow);
+        if (planes_overlap(out, (size_t)out_stride * esz, (size_t)ow * esz, conf, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh))
+            return fail(err, WS_ERR_ARG, "the confidence plane overlaps the map");
+    }
+    if (!ctx) return fail(nullptr, WS_ERR_ARG, "null context");
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t px = (size_t)ow * oh;
+    HostSpan sp[4];
+    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left))) != WS_OK) return rc;
+    if ((rc = ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right))) != WS_OK) return rc;
+    if ((rc = ensure(&ctx->err, ctx->d_out, (conf ? 2 : 1) * px * sizeof(float))) != WS_OK) return rc;
+    span_set(sp[2], out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)oh, &ctx->h_out);
+    if (conf) span_set(sp[3], conf, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh, &ctx->h_aux[0]);
+    spans_attach(sp, 4);
+    rc = [&]() -> int {
+        ws_image dl, dr;
+        WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
+        WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
+        float *map = static_cast<float *>(ctx->d_out.p), *cmap = conf ? map + px : nullptr;
+        if (const int r = enqueue_sgm(ctx, p, sgm, &dl, &dr, map, ow, s, uq, cmap, ow); r != WS_OK) return r;
+        WS_HIP(&ctx->err, span_download(sp[2], 0, (size_t)out_stride, map, (size_t)ow, (size_t)oh, kWireF32, esz, s));
+        if (conf) WS_HIP(&ctx->err, span_download(sp[3], 0, (size_t)conf_stride, cmap, (size_t)ow, (size_t)oh, kWireF32, 4, s));
+        return WS_OK;
+    }();
+    for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
+    ctx->last_wire = kWireF32;
+    return finish_host_call(ctx, rc, sp, 4, {s}, "uniqueness host call");
+}
+
+int ws_last_unique_counts(ws_context *ctx, unsigned long long counts[2])
+{
+    if (!ctx || !counts) return WS_ERR_ARG;
+    SgmState &S = ctx->sgm;
+    if (!S.unique_ran) return fail(&ctx->err, WS_ERR_ARG, "no uniqueness call has run on this context");
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    if (S.busy) WS_HIP(&ctx->err, hipEventSynchronize(S.ev));
+    const auto *c = reinterpret_cast<const unsigned long long *>(S.counts_host.p);
+    counts[0] = c[0];
+    counts[1] = c[1];
+    return WS_OK;
 }
 
 } // extern "C"

@@ -35,6 +35,15 @@ struct SgmArgs {
     int out_pitch;
 };
 
+// The uniqueness test and the confidence plane of one winner pass (ws_unique_wta_kernel).
+struct UniqueArgs {
+    int ratio;                  // 0 .. 100
+    float *conf;                // the confidence plane, or null
+    int conf_pitch;
+    unsigned long long *counts; // {failed nodes, nodes}: zero on entry, one atomic add per wave and word
+    int num_cus;
+};
+
 // The largest window cost of a search with cost WS_COST_* (a square window of bs x bs pixels: three channels, or the bits
 // of a census descriptor).
 inline uint64_t sgm_cost_max(int cost, int block_size)
@@ -45,6 +54,9 @@ inline uint64_t sgm_cost_max(int cost, int block_size)
 
 // The cost plane (a census cost: from the match kernel of ws_ct.hip), the paths (`paths` 4 or 8, one launch each, summed in place in order on s) and the winner.
 hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s);
+// The same volumes, then the winner with the uniqueness test.  paths == 0: the block route -- no path kernel runs and the
+// winner reads C (a.sum is not touched).
+hipError_t launch_unique(const SgmArgs &a, const UniqueArgs &u, int paths, hipStream_t s);
 
 } // namespace wsamd
 #pragma GCC visibility pop

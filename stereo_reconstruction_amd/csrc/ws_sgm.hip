@@ -13,9 +13,14 @@
 //     two waves of a launch touch the same sums.
 //   * ws_sgm_wta_kernel: one wave per pixel: the minimum of (S, tie tag) over the candidates, the parabola on S, and
 //     the fallbacks; lane 0 writes the float32 value.
+//   * ws_unique_wta_kernel: that winner with the uniqueness test and the confidence of include/ws_stereo.h, on S or
+//     (block route, no path kernel) on C itself.  Each lane keeps its best key and its runner-up's value, so the curve
+//     is read once: the rival minimum m2 is a second wave minimum over what the lanes still hold.
 // Every store is a plain vector store.
 #include "ws_sgm.h"
 #include "ws_ct.h"
+
+#include <type_traits>
 
 namespace wsamd {
 
@@ -28,6 +33,7 @@ constexpr int kSgmMaxHalf = 31;                      // block_size <= 63
 constexpr int kSgmCols = kSgmTile + 2 * kSgmMaxHalf; // column sums a tile needs at most
 constexpr int kSgmColsPerWave = (kSgmCols + 3) / 4;
 constexpr uint32_t kNoCandidate = 0xffffffffu;
+constexpr int kUniqueBlocksPerCu = 8;                // uniqueness winner: 32 waves per CU, all resident
 static_assert(kSgmThreads == 256 && kSgmTile == 64, "four waves, 16 output columns each");
 static_assert(kSgmMaxNd <= 64 * 32 && kSgmMaxNd < 4096, "32 disparities per lane; 12-bit tie tags");
 
@@ -301,6 +307,81 @@ __global__ __launch_bounds__(kSgmThreads) void ws_sgm_wta_kernel(SgmArgs a)
     }
 }
 
+// The winner with the rival minimum (uniqueness section of include/ws_stereo.h).  A lane visits j = lo + lane + 64 k, so
+// jb - 1, jb, jb + 1 lie in three different lanes and a lane loses at most one entry to the exclusion: its best if
+// that is one of the three, else an entry that is no smaller than its best.  Hence the lane's offer to m2 is its best,
+// or its runner-up when its best is excluded.  VT: C as uint16_t / uint32_t, S as uint32_t / unsigned long long.
+// The kernel is bound by the instructions a pixel takes, not by the bytes of its curve, so what is the same in every
+// lane is kept scalar: the pixel index comes from the wave's number read as a uniform value, which makes the interval,
+// the row / column split and the branches on the pixel's kind scalar work; the second minimum runs on 32-bit values
+// where the stored type allows; and the confidence's division is done only when a plane was given.
+template <typename VT>
+__global__ __launch_bounds__(kSgmThreads) void ws_unique_wta_kernel(SgmArgs a, const VT *vol, UniqueArgs u)
+{
+    using MT = std::conditional_t<sizeof(VT) <= 4, uint32_t, unsigned long long>; // an offer to m2
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = (uint32_t)a.w * (uint32_t)a.h; // (< 2^31: ws_validate_sgm)
+    const uint32_t waves = gridDim.x * (kSgmThreads / 64);
+    const uint32_t first = blockIdx.x * (kSgmThreads / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    unsigned long long failed = 0, nodes = 0;
+    for (uint32_t i = first; i < n; i += waves) {
+        const uint32_t y = i / (uint32_t)a.w, x = i - y * (uint32_t)a.w;
+        const uint32_t kr = a.kr[i];
+        float v = 0.0f, conf = 0.0f;
+        if (kr == kNoCandidate) {
+            v = (float)(a.right ? -(int)x : (int)x);
+        } else if (kr != 0) {
+            const int lo = (int)(kr & 0xffff), hi = (int)(kr >> 16);
+            const VT *s = vol + (size_t)i * a.nd;
+            unsigned long long best = ~0ull; // the lane's best (value, tag) ...
+            MT second = ~(MT)0;              // ... and its runner-up's value
+            bool two = false;                // ... if it has one
+            for (int j = lo + lane; j < hi; j += 64) {
+                const unsigned long long val = (unsigned long long)s[j];
+                const unsigned long long k = val << 12 | (unsigned)(a.right ? j : 4095 - j);
+                const MT loser = k < best ? (MT)(best >> 12) : (MT)val;
+                two = best != ~0ull;
+                best = k < best ? k : best;
+                second = loser < second ? loser : second;
+            }
+            const unsigned long long key = wave_min64(best);
+            const int jb = a.right ? (int)(key & 4095) : 4095 - (int)(key & 4095);
+            const unsigned long long smin = key >> 12;
+            const int jl = a.right ? (int)(best & 4095) : 4095 - (int)(best & 4095);
+            const bool mine = best != ~0ull && abs(jl - jb) >= 2; // the lane's best is a rival; else its runner-up is
+            const bool contested = __ballot(mine || two) != 0;
+            MT offer = mine ? (MT)(best >> 12) : second; // (a lane without a rival offers the largest value)
+            if constexpr (sizeof(MT) == 4) offer = wave_min(offer);
+            else offer = wave_min64(offer);
+            const unsigned long long m2 = offer;
+            v = (float)(a.d0 + jb);
+            if (a.subpixel && jb - 1 >= lo && jb + 1 < hi) {
+                const long long sm = (long long)s[jb - 1], s0 = (long long)s[jb], sp = (long long)s[jb + 1];
+                const long long num = sm - sp, den = sm - 2 * s0 + sp;
+                if (den > 0) v = v + (float)((double)num / (2.0 * (double)den));
+            }
+            conf = 1.0f;
+            ++nodes;
+            if (contested) {
+                conf = 0.0f;
+                if (u.conf && m2 > 0) conf = (float)((double)(m2 - smin) / (double)m2);
+                if (m2 * (unsigned long long)(100 - u.ratio) < smin * 100ull) {
+                    v = 0.0f;
+                    ++failed;
+                }
+            }
+        }
+        if (lane == 0) {
+            a.out[(size_t)y * a.out_pitch + x] = v;
+            if (u.conf) u.conf[(size_t)y * u.conf_pitch + x] = conf;
+        }
+    }
+    if (lane == 0 && nodes) { // (failed and nodes are uniform over the wave)
+        if (failed) atomicAdd(u.counts, failed);
+        atomicAdd(u.counts + 1, nodes);
+    }
+}
+
 template <int NJ, typename CT, typename ST>
 hipError_t launch_paths(const SgmArgs &a, int paths, hipStream_t s)
 {
@@ -327,7 +408,8 @@ hipError_t launch_paths_nj(const SgmArgs &a, int paths, hipStream_t s)
 
 } // namespace
 
-hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s)
+// The candidate intervals, the cost plane and, with paths > 0, the sums, on s.
+static hipError_t launch_volumes(const SgmArgs &a, int paths, hipStream_t s)
 {
     const long long n = (long long)a.w * a.h;
     const int grid = (int)std::min<long long>((n + kSgmThreads - 1) / kSgmThreads, 1 << 20);
@@ -344,16 +426,41 @@ hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s)
             if (const hipError_t e = launch_census_match(c, true, s); e != hipSuccess) return e;
         } else if (a.cost16) ws_sgm_cost_kernel<uint16_t><<<(int)blocks, kSgmThreads, 0, s>>>(a);
         else ws_sgm_cost_kernel<uint32_t><<<(int)blocks, kSgmThreads, 0, s>>>(a);
-        hipError_t e;
-        if (a.cost16 && !a.sum64) e = launch_paths_nj<uint16_t, uint32_t>(a, paths, s);
-        else if (a.cost16) e = launch_paths_nj<uint16_t, unsigned long long>(a, paths, s);
-        else if (!a.sum64) e = launch_paths_nj<uint32_t, uint32_t>(a, paths, s);
-        else e = launch_paths_nj<uint32_t, unsigned long long>(a, paths, s);
-        if (e != hipSuccess) return e;
+        if (paths > 0) {
+            hipError_t e;
+            if (a.cost16 && !a.sum64) e = launch_paths_nj<uint16_t, uint32_t>(a, paths, s);
+            else if (a.cost16) e = launch_paths_nj<uint16_t, unsigned long long>(a, paths, s);
+            else if (!a.sum64) e = launch_paths_nj<uint32_t, uint32_t>(a, paths, s);
+            else e = launch_paths_nj<uint32_t, unsigned long long>(a, paths, s);
+            if (e != hipSuccess) return e;
+        }
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s)
+{
+    if (const hipError_t e = launch_volumes(a, paths, s); e != hipSuccess) return e;
+    const long long n = (long long)a.w * a.h;
     const int wgrid = (int)std::min<long long>((n + 3) / 4, 1 << 20);
     if (a.sum64) ws_sgm_wta_kernel<unsigned long long><<<wgrid, kSgmThreads, 0, s>>>(a);
     else ws_sgm_wta_kernel<uint32_t><<<wgrid, kSgmThreads, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_unique(const SgmArgs &a, const UniqueArgs &u, int paths, hipStream_t s)
+{
+    if (const hipError_t e = launch_volumes(a, paths, s); e != hipSuccess) return e;
+    // a grid the device holds at once: each wave walks its share of the pixels and adds to the counts once at its end
+    const long long n = (long long)a.w * a.h;
+    const int wgrid = (int)std::min<long long>((n + 3) / 4, (long long)kUniqueBlocksPerCu * std::max(1, u.num_cus));
+    if (paths > 0) {
+        if (a.sum64) ws_unique_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const unsigned long long *>(a.sum), u);
+        else ws_unique_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint32_t *>(a.sum), u);
+    } else {
+        if (a.cost16) ws_unique_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint16_t *>(a.cost), u);
+        else ws_unique_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint32_t *>(a.cost), u);
+    }
     return hipGetLastError();
 }
 

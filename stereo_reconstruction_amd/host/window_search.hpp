@@ -171,7 +171,41 @@ public:
     MatF64 computeDisparityMapLeftSGM(int P1, int P2, int paths = 8) { return sgm(WS_VIEW_LEFT, P1, P2, paths); }
     MatF64 computeDisparityMapRightSGM(int P1, int P2, int paths = 8) { return sgm(WS_VIEW_RIGHT, P1, P2, paths); }
 
+    // Extension: OpenCV's uniquenessRatio (rules in ws_stereo.h).  The maps of computeDisparityMapLeft(1) /
+    // computeDisparityMapRight(1), or with paths = 4 or 8 those of the SGM calls above, with every pixel whose best cost
+    // does not beat its best rival (two or more disparities away) by uniquenessRatio percent set to 0, no disparity.
+    // confidence, if not null, receives the margin itself: float32, the map's size, 1 = unrivalled, 0 = a tie.
+    MatF64 computeDisparityMapLeftUnique(int uniquenessRatio, std::vector<float> *confidence = nullptr, int paths = 0, int P1 = 0,
+                                         int P2 = 0)
+    {
+        return unique(WS_VIEW_LEFT, uniquenessRatio, confidence, paths, P1, P2);
+    }
+    MatF64 computeDisparityMapRightUnique(int uniquenessRatio, std::vector<float> *confidence = nullptr, int paths = 0, int P1 = 0,
+                                          int P2 = 0)
+    {
+        return unique(WS_VIEW_RIGHT, uniquenessRatio, confidence, paths, P1, P2);
+    }
+
 private:
+    MatF64 unique(int view, int ratio, std::vector<float> *confidence, int paths, int P1, int P2)
+    {
+        const ws_params p = params(view, 1.0);
+        ws_sgm_params sp;
+        sp.paths = paths;
+        sp.p1 = P1;
+        sp.p2 = P2;
+        ws_unique_params uq;
+        uq.ratio = ratio;
+        const bool left = view == WS_VIEW_LEFT;
+        MatF64 out(left ? leftImage_.rows : rightImage_.rows, left ? leftImage_.cols : rightImage_.cols);
+        if (confidence) confidence->assign(static_cast<size_t>(out.rows) * out.cols, 0.0f);
+        const ws_image li = detail::to_c(leftImage_), ri = detail::to_c(rightImage_);
+        const int rc = ws_search_unique_host(device_.get(), &p, paths ? &sp : nullptr, &uq, &li, &ri, out.ptr(), out.cols, WS_OUT_F64,
+                                             confidence ? confidence->data() : nullptr, out.cols);
+        if (rc != WS_OK) throw Error(rc, ws_last_error(device_.get()));
+        return out;
+    }
+
     MatF64 sgm(int view, int P1, int P2, int paths)
     {
         const ws_params p = params(view, 1.0);
