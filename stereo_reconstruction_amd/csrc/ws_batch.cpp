@@ -33,12 +33,6 @@ int fail(ws_batch *b, int code, const char *fmt, ...)
     return code;
 }
 
-void out_dims(const ws_params &p, const ws_image &l, const ws_image &r, int *w, int *h)
-{
-    *w = p.view == WS_VIEW_LEFT ? l.width : r.width;
-    *h = p.view == WS_VIEW_LEFT ? l.height : r.height;
-}
-
 long long job_nd(const ws_params &p)
 {
     return p.view == WS_VIEW_LEFT ? (long long)p.max_disparity
@@ -64,7 +58,7 @@ int check_job(ws_batch *b, const ws_job &j, int i, bool outputs)
     if (!outputs) return WS_OK;
     if (!j.out || (j.out_dtype != WS_OUT_F32 && j.out_dtype != WS_OUT_F64)) return fail(b, WS_ERR_ARG, "job %d: bad output", i);
     int ow, oh;
-    out_dims(j.params, j.left, j.right, &ow, &oh);
+    wsamd::map_dims(&j.params, &j.left, &j.right, &ow, &oh);
     if (j.out_stride < ow) return fail(b, WS_ERR_ARG, "job %d: out_stride %d < width %d", i, j.out_stride, ow);
     return WS_OK;
 }
@@ -78,7 +72,7 @@ int make_plan(ws_batch *b, const ws_job *jobs, int n_jobs, int n_workers, int ba
     bool can = bands == 1;
     for (int i = 0; i < n_jobs; ++i) {
         int ow, oh;
-        out_dims(jobs[i].params, jobs[i].left, jobs[i].right, &ow, &oh);
+        wsamd::map_dims(&jobs[i].params, &jobs[i].left, &jobs[i].right, &ow, &oh);
         shapes.push_back({ow, oh, job_nd(jobs[i].params)});
         can = can && band_ok(jobs[i]) && jobs[i].params.block_size == jobs[0].params.block_size &&
               shapes.back().nd == shapes[0].nd && shapes[0].nd >= 1;
@@ -177,7 +171,7 @@ int ws_batch_search_host(ws_batch *b, ws_job *jobs, int n_jobs, int bands, int m
     auto run_item = [&](int w, const wsbatch::Item &it) -> int {
         const ws_job &j = jobs[it.job];
         int ow, oh;
-        out_dims(j.params, j.left, j.right, &ow, &oh);
+        wsamd::map_dims(&j.params, &j.left, &j.right, &ow, &oh);
         if (it.y0 == 0 && it.y1 == oh)
             return ws_enqueue_host(b->ctx[(size_t)w], &j.params, &j.left, &j.right, j.out, j.out_stride, j.out_dtype);
         // a row band (equal image heights): the sub-images under its rows and the window's halo
@@ -185,7 +179,7 @@ int ws_batch_search_host(ws_batch *b, ws_job *jobs, int n_jobs, int bands, int m
         const int a = it.y0 - half > 0 ? it.y0 - half : 0, e = it.y1 + half < oh ? it.y1 + half : oh;
         const ws_image l{j.left.data + (size_t)a * j.left.stride, j.left.width, e - a, j.left.stride};
         const ws_image r{j.right.data + (size_t)a * j.right.stride, j.right.width, e - a, j.right.stride};
-        const size_t esz = j.out_dtype == WS_OUT_F32 ? 4 : 8;
+        const size_t esz = (size_t)wsamd::out_elem_size(j.out_dtype);
         void *out = static_cast<uint8_t *>(j.out) + (size_t)it.y0 * j.out_stride * esz;
         return wsamd::enqueue_host_rows(b->ctx[(size_t)w], &j.params, &l, &r, out, j.out_stride, j.out_dtype, it.y0 - a, it.y1 - it.y0);
     };

@@ -83,6 +83,38 @@ int wsamd::finish_host_call(ws_context *ctx, int rc, HostSpan *sp, int count, st
     return rc;
 }
 
+int wsamd::PairHostCall::open()
+{
+    if (const int rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left)); rc != WS_OK) return rc;
+    return ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right));
+}
+
+int wsamd::PairHostCall::upload()
+{
+    WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
+    WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
+    return WS_OK;
+}
+
+int wsamd::PairHostCall::close(int rc, int count, int wire, bool device_status, const char *what, std::initializer_list<hipStream_t> streams)
+{
+    if (wire >= 0) {
+        for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
+        ctx->last_wire = wire;
+    }
+    rc = streams.size() ? finish_host_call(ctx, rc, sp, count, streams, what) : finish_host_call(ctx, rc, sp, count, {s}, what);
+    return rc == WS_OK && device_status ? check_device_status(ctx) : rc;
+}
+
+int wsamd::read_counts(ws_context *ctx, CountPair &c, ScratchLease &lease, const char *none, unsigned long long out[2])
+{
+    if (!c.ran) return fail(&ctx->err, WS_ERR_ARG, "%s", none);
+    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
+    if (lease.busy) WS_HIP(&ctx->err, hipEventSynchronize(lease.ev));
+    memcpy(out, c.host.p, CountPair::kBytes);
+    return WS_OK;
+}
+
 extern "C" {
 
 int ws_version(void) { return WS_VERSION; }
@@ -128,7 +160,6 @@ int ws_create(int device, ws_context **out)
         (e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreate(&ctx->ev0)) != hipSuccess || (e = hipEventCreate(&ctx->ev1)) != hipSuccess ||
         (e = hipEventCreate(&ctx->searcher.evk0)) != hipSuccess || (e = hipEventCreate(&ctx->searcher.evk1)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&ctx->searcher.ev_scratch, hipEventDisableTiming)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&ctx->jobs[0].ev_h2d, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&ctx->jobs[0].ev_done, hipEventDisableTiming)) != hipSuccess ||
@@ -157,19 +188,17 @@ void ws_destroy(ws_context *ctx)
     (void)hipSetDevice(ctx->device);
     for (hipStream_t s : {ctx->stream, ctx->copy_stream, ctx->down_stream})
         if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-    for (hipEvent_t e : {ctx->ev0, ctx->ev1, ctx->searcher.evk0, ctx->searcher.evk1, ctx->searcher.ev_scratch, ctx->jobs[0].ev_h2d,
-                         ctx->jobs[0].ev_done, ctx->jobs[1].ev_h2d, ctx->jobs[1].ev_done})
+    for (hipEvent_t e : {ctx->ev0, ctx->ev1, ctx->searcher.evk0, ctx->searcher.evk1, ctx->jobs[0].ev_h2d, ctx->jobs[0].ev_done,
+                         ctx->jobs[1].ev_h2d, ctx->jobs[1].ev_done})
         if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < ws_context::kMaxBands; ++i)
         for (hipEvent_t e : {ctx->ev_band_up[i], ctx->ev_band_done[i], ctx->ev_band_down[i]})
             if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_mesh)
         if (e) (void)hipEventDestroy(e);
-    if (ctx->lr.ev) (void)hipEventDestroy(ctx->lr.ev);
-    if (ctx->speckle.ev) (void)hipEventDestroy(ctx->speckle.ev);
-    if (ctx->sgm.ev) (void)hipEventDestroy(ctx->sgm.ev);
-    // every buffer goes with its owner, on this device, with nothing using it.  A batch never waited for: its maps are NOT
-    // handed over -- only ws_wait delivers, and a caller who abandoned the batch may have freed the buffers they go to
+    // every buffer and every lease's event goes with its owner, on this device, with nothing using it.  A batch never
+    // waited for: its maps are NOT handed over -- only ws_wait delivers, and a caller who abandoned the batch may have
+    // freed the buffers they go to
     delete ctx;
 }
 
@@ -188,9 +217,9 @@ int ws_plan(const ws_params *p, const ws_image *left, const ws_image *right, int
     int rc = check_params(nullptr, p, left, right);
     if (rc != WS_OK) return rc;
     if (p->view != WS_VIEW_LINEAR && is_census(p->cost)) { // the census match kernel: no marching region, one kernel for the map
-        const int ow = p->view == WS_VIEW_LEFT ? left->width : right->width, oh = p->view == WS_VIEW_LEFT ? left->height : right->height;
-        int d0, nd;
-        census_range(p, left, &d0, &nd);
+        int ow, oh, d0, nd;
+        map_dims(p, left, right, &ow, &oh);
+        disparity_range(p, left, &d0, &nd);
         out->kernel_kind = 2;
         out->threads = kCtThreads;
         out->tiles = (ow + kCtTile - 1) / kCtTile;
@@ -379,36 +408,30 @@ int ws_search_host(ws_context *ctx, const ws_params *p, const ws_image *left, co
     // The caller's buffers for the duration of the call (HostSpan): caller-pinned or staged -- every
     // host copy of this library goes the same way, whatever the band setting of the moment, and none through the
     // runtime's pageable path.
-    HostSpan sp[3];
-    const int wire = wire_for(p, left, right), esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    PairHostCall call(ctx, left, right);
+    HostSpan *sp = call.sp;
+    const int wire = wire_for(p, left, right), esz = out_elem_size(out_dtype);
     const int half = (p->block_size - 1) / 2;
     const size_t map_px = (size_t)ow * (oh + 2 * half * nb); // (in bands: each band's map with its halo rows)
-    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left))) != WS_OK) return rc;
-    if ((rc = ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right))) != WS_OK) return rc;
+    if ((rc = call.open()) != WS_OK) return rc;
     if ((rc = ensure(&ctx->err, ctx->d_out, map_px * 4)) != WS_OK) return rc;
     if (wire == kWireI16 && (rc = ensure(&ctx->err, ctx->d_out16, map_px * 2)) != WS_OK) return rc;
     span_set(sp[2], out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)oh, &ctx->h_out);
     if (nb) {
         rc = search_host_banded(ctx, p, left, right, sp, wire, esz, ow, oh, nb);
-    } else {
-        spans_attach(sp, 3);
-        rc = [&]() -> int {
-            ws_image dl, dr;
-            WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
-            WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
-            float *dout = static_cast<float *>(ctx->d_out.p);
-            int16_t *dout16 = wire == kWireI16 ? static_cast<int16_t *>(ctx->d_out16.p) : nullptr;
-            if (const int rc2 = search(ctx->searcher, &ctx->err, p, &dl, &dr, dout, ow, dout16, ctx->status_dev, s); rc2 != WS_OK) return rc2;
-            const void *src = wire == kWireI16 ? static_cast<const void *>(dout16) : static_cast<const void *>(dout);
-            WS_HIP(&ctx->err, span_download(sp[2], 0, (size_t)out_stride, src, (size_t)ow, (size_t)oh, wire, esz, s));
-            return WS_OK;
-        }();
+        return call.close(rc, 3, wire, true, "banded host call", {ctx->copy_stream, s, ctx->down_stream});
     }
-    for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
-    ctx->last_wire = wire;
-    rc = nb ? finish_host_call(ctx, rc, sp, 3, {ctx->copy_stream, s, ctx->down_stream}, "banded host call")
-            : finish_host_call(ctx, rc, sp, 3, {s}, "host call");
-    return rc == WS_OK ? check_device_status(ctx) : rc;
+    spans_attach(sp, 3);
+    rc = [&]() -> int {
+        if (const int r = call.upload(); r != WS_OK) return r;
+        float *dout = static_cast<float *>(ctx->d_out.p);
+        int16_t *dout16 = wire == kWireI16 ? static_cast<int16_t *>(ctx->d_out16.p) : nullptr;
+        if (const int r = search(ctx->searcher, &ctx->err, p, &call.dl, &call.dr, dout, ow, dout16, ctx->status_dev, s); r != WS_OK) return r;
+        const void *src = wire == kWireI16 ? static_cast<const void *>(dout16) : static_cast<const void *>(dout);
+        WS_HIP(&ctx->err, span_download(sp[2], 0, (size_t)out_stride, src, (size_t)ow, (size_t)oh, wire, esz, s));
+        return WS_OK;
+    }();
+    return call.close(rc, 3, wire, true, "host call");
 }
 
 // The batched host path keeps two pairs in flight: while one is searched (context stream) the next
@@ -419,7 +442,7 @@ static int flush_job(ws_context *ctx, Job &j)
     if (!j.pending) return WS_OK;
     j.pending = false;
     WS_HIP(&ctx->err, hipStreamWaitEvent(ctx->copy_stream, j.ev_done, 0));
-    const int esz = j.dtype == WS_OUT_F32 ? 4 : 8;
+    const int esz = out_elem_size(j.dtype);
     const size_t first = (size_t)j.row0 * j.w;
     const void *src = j.wire == kWireI16 ? static_cast<const void *>(static_cast<const int16_t *>(j.out16.p) + first)
                                          : static_cast<const void *>(static_cast<const float *>(j.out.p) + first);
@@ -475,7 +498,7 @@ int wsamd::enqueue_host_rows(ws_context *ctx, const ws_params *p, const ws_image
         return rc;
     uint8_t *d_left = static_cast<uint8_t *>(job.in.p), *d_right = d_left + off_r;
     hipStream_t cs = ctx->copy_stream;
-    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    const int esz = out_elem_size(out_dtype);
     span_set(sp[2], out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)map_rows, &job.h_out);
     spans_attach(sp, 3);
     const size_t first = ctx->batch_spans.size();
@@ -648,30 +671,28 @@ int ws_search_unrectified_host(ws_context *ctx, const ws_params *p, const ws_ima
         return fail(&ctx->err, rc, "%s", ws_last_error(nullptr));
     const ws_image shape_l{left->data, lw, lh, 3 * lw}, shape_r{right->data, rw, rh, 3 * rw};
     if ((rc = check_params(&ctx->err, p, &shape_l, &shape_r)) != WS_OK) return rc;
-    const bool lv = p->view == WS_VIEW_LEFT;
-    const int mw = lv ? lw : rw, mh = lv ? lh : rh; // the rectified map
+    int mw, mh; // the rectified map
+    map_dims(p, &shape_l, &shape_r, &mw, &mh);
     if ((rect_left && rect_left_stride < 3 * lw) || (rect_right && rect_right_stride < 3 * rw))
         return fail(&ctx->err, WS_ERR_ARG, "rectified image stride below 3 * width");
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    // the caller's buffers for the duration of the call (HostSpan, like ws_search_host)
-    HostSpan sp[5];
-    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left))) != WS_OK) return rc;
-    if ((rc = ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right))) != WS_OK) return rc;
+    PairHostCall call(ctx, left, right);
+    HostSpan *sp = call.sp;
+    if ((rc = call.open()) != WS_OK) return rc;
     if ((rc = ensure(&ctx->err, ctx->d_rect_left, (size_t)lw * lh * 3)) != WS_OK) return rc;
     if ((rc = ensure(&ctx->err, ctx->d_rect_right, (size_t)rw * rh * 3)) != WS_OK) return rc;
     if ((rc = ensure(&ctx->err, ctx->d_out, (size_t)mw * mh * 4)) != WS_OK) return rc;
     if ((rc = ensure(&ctx->err, ctx->d_out64, (size_t)ow * oh * 4)) != WS_OK) return rc;
-    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    const int esz = out_elem_size(out_dtype);
     span_set(sp[2], out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)oh, &ctx->h_out);
     if (rect_left) span_set(sp[3], rect_left, (size_t)rect_left_stride, 3 * (size_t)lw, (size_t)lh, &ctx->h_aux[0]);
     if (rect_right) span_set(sp[4], rect_right, (size_t)rect_right_stride, 3 * (size_t)rw, (size_t)rh, &ctx->h_aux[1]);
     spans_attach(sp, 5);
     uint8_t *drl = static_cast<uint8_t *>(ctx->d_rect_left.p), *drr = static_cast<uint8_t *>(ctx->d_rect_right.p);
     rc = [&]() -> int {
-        ws_image dl, dr;
-        WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
-        WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
+        if (const int r = call.upload(); r != WS_OK) return r;
+        const ws_image &dl = call.dl, &dr = call.dr;
         // warpPerspective(leftImage_, .., H_, size), warpPerspective(rightImage_, .., Hp_, size) (rectification.cpp:486-493)
         WS_HIP(&ctx->err, launch_rectify(dl.data, dl.width, dl.height, dl.stride, h_inv, drl, lw, lh, 3 * lw, s));
         WS_HIP(&ctx->err, launch_rectify(dr.data, dr.width, dr.height, dr.stride, hp_inv, drr, rw, rh, 3 * rw, s));
@@ -686,8 +707,7 @@ int ws_search_unrectified_host(ws_context *ctx, const ws_params *p, const ws_ima
         if (rect_right) WS_HIP(&ctx->err, span_download_bytes(sp[4], 0, (size_t)rect_right_stride, drr, 3 * (size_t)rw, (size_t)rh, s));
         return WS_OK;
     }();
-    rc = finish_host_call(ctx, rc, sp, 5, {s}, "unrectified host call");
-    return rc == WS_OK ? check_device_status(ctx) : rc;
+    return call.close(rc, 5, -1, true, "unrectified host call"); // (this call has never reported its paths)
 }
 
 // ---- consumers of the map (src/Reconstruction/reconstruction.cpp) ----------------------

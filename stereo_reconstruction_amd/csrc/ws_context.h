@@ -1,5 +1,7 @@
 // ws_context.h -- the context behind the C-ABI's opaque ws_context, for the sources that implement its entry points
-// (ws_capi.cpp, ws_lr.cpp, ws_speckle.cpp, ws_sgm.cpp), and the epilogue of their synchronous host calls.
+// (ws_capi.cpp, ws_lr.cpp, ws_speckle.cpp, ws_sgm.cpp), and what those share: the counter pair behind ws_last_*_counts,
+// the frame of a synchronous host call on a pair of images (PairHostCall) and the epilogue of every synchronous host
+// call.
 #pragma once
 
 #include "ws_capi_internal.h"
@@ -27,44 +29,54 @@ struct Job { // one pair in flight on the batched host path
     int out_span = -1;       // index of this pair's output span in ws_context::batch_spans
 };
 
+// Two unsigned long long that come down behind a call, for ws_last_*_counts: their place on the device (behind the
+// kernel's own slot words, if it has any), the pinned host copy, and whether a call has sent them on their way.
+struct CountPair {
+    DevBuf dev;
+    HostBuf host;
+    bool ran = false; // a call was enqueued: host holds (or will hold) its counts
+    static constexpr size_t kBytes = 2 * sizeof(unsigned long long);
+    // room for slot_bytes of the kernel's own in front of the pair, and the host copy's
+    int reserve(std::string *err, size_t slot_bytes)
+    {
+        if (const int rc = ensure(err, dev, slot_bytes + kBytes); rc != WS_OK) return rc;
+        WS_HIP(err, host_ensure(host, kBytes));
+        return WS_OK;
+    }
+    // the pair at `sums` (in dev) -> host, on s, behind the kernels that write it: the end of a call's enqueue
+    int fetch(std::string *err, const unsigned long long *sums, hipStream_t s)
+    {
+        WS_HIP(err, hipMemcpyAsync(host.p, sums, kBytes, hipMemcpyDeviceToHost, s));
+        ran = true;
+        return WS_OK;
+    }
+};
+
 // The left-right check's device memory (ws_lr.cpp): the two raw maps of ws_search_lr_*, the per-pixel states the fill
-// reads, and the failure counters that ws_last_lr_counts reads.  Shared by every check of the context: a check on another
-// stream than the previous one first waits (on the device) for that one, as the Searcher's scratch planes do.
+// reads, and the failure counters that ws_last_lr_counts reads.  Shared by every check of the context, under its lease.
 struct LrState {
-    DevBuf raw;              // ws_search_lr_*: the left view's map, then the right view's (float32, dense)
-    DevBuf states;           // one byte per pixel of both maps (kLrEmpty / kLrPassed / kLrFailed)
-    DevBuf counts;           // the check kernel's failure counters (lr_slot_words()), then their sums: left map, right map
-    HostBuf counts_host;     // ... copied here behind the check kernel
-    hipEvent_t ev = nullptr; // end of the last check
-    hipStream_t stream = nullptr;
-    bool busy = false; // ev is recorded on `stream`
-    bool ran = false;  // a check was enqueued: counts_host holds (or will hold) its counts
+    ScratchLease lease;
+    DevBuf raw;       // ws_search_lr_*: the left view's map, then the right view's (float32, dense)
+    DevBuf states;    // one byte per pixel of both maps (kLrEmpty / kLrPassed / kLrFailed)
+    CountPair counts; // the check kernel's failure counters (lr_slot_words()), then their sums: left map, right map
 };
 
 // The speckle filter's device memory (ws_speckle.cpp): the four int planes of the labelling, the counters, their sums on
-// the way to the host.  Shared by every filter of the context, with the same cross-stream wait as LrState.
+// the way to the host.  Shared by every filter of the context, under its lease.
 struct SpeckleState {
-    DevBuf planes;           // label, parent, count, local: w*h ints each (SpeckleArgs)
-    DevBuf counts;           // speckle_slot_words() counters, then their sums: pixels set, regions removed
-    HostBuf counts_host;     // ... copied here behind the filter
-    hipEvent_t ev = nullptr; // end of the last filter
-    hipStream_t stream = nullptr;
-    bool busy = false; // ev is recorded on `stream`
-    bool ran = false;  // a filter was enqueued: counts_host holds (or will hold) its counts
+    ScratchLease lease;
+    DevBuf planes;    // label, parent, count, local: w*h ints each (SpeckleArgs)
+    CountPair counts; // speckle_slot_words() counters, then their sums: pixels set, regions removed
 };
 
 // Semi-global matching's device memory (ws_sgm.cpp): the candidate intervals, the cost plane and the path sums of one
-// call, grown to what the call needs.  Shared by every SGM call of the context, with the same cross-stream wait as
-// LrState; the searches' own scratch (Searcher) is apart from it.  The uniqueness calls (ws_search_unique_*) are SGM
-// calls in this respect: the same scratch, the same event, and their two counters beside it.
+// call, grown to exactly what the call needs.  Shared by every SGM call of the context, under its lease; the searches'
+// own scratch (Searcher) is apart from it.  The uniqueness calls (ws_search_unique_*) are SGM calls in this respect: the
+// same scratch, the same lease, and their two counters beside it.
 struct SgmState {
+    ScratchLease lease;
     DevBuf scratch;
-    DevBuf counts;           // ws_search_unique_*: {failed nodes, nodes}, zeroed on the stream before the winner kernel
-    HostBuf counts_host;     // ... copied here behind it
-    bool unique_ran = false; // such a call was enqueued: counts_host holds (or will hold) its counts
-    hipEvent_t ev = nullptr; // end of the last SGM call
-    hipStream_t stream = nullptr;
-    bool busy = false; // ev is recorded on `stream`
+    CountPair counts; // ws_search_unique_*: {failed nodes, nodes}, zeroed on the stream before the winner kernel
 };
 
 } // namespace wsamd
@@ -112,6 +124,27 @@ int check_device_status(ws_context *ctx);
 // The end of a synchronous host call: the streams idle (after an error too: nothing may still be copying when the spans are
 // released), staged downloads handed over -- or dropped if the call or a stream failed -- and a stream's error reported.
 int finish_host_call(ws_context *ctx, int rc, HostSpan *sp, int count, std::initializer_list<hipStream_t> streams, const char *what);
+
+// A synchronous host call on a pair of images, on the context's stream: open(), the caller's output spans from sp[2] on
+// and spans_attach, upload(), the call's own work and downloads, close().
+struct PairHostCall {
+    ws_context *ctx;
+    const ws_image *left, *right;
+    hipStream_t s;  // the context's stream
+    HostSpan sp[5]; // the caller's buffers for the duration of the call: the images, then the outputs
+    ws_image dl, dr; // the images as the device holds them (upload)
+    PairHostCall(ws_context *c, const ws_image *l, const ws_image *r) : ctx(c), left(l), right(r), s(c->stream) {}
+    int open();   // sp[0], sp[1] and room in d_left / d_right
+    int upload(); // both images -> d_left / d_right on s
+    // How the images and the map crossed and the map's wire format for ws_last_host_paths / ws_last_wire_format
+    // (wire < 0: the call leaves them alone), then finish_host_call on `streams` (none: s) with the first `count`
+    // spans, then -- for a call that ran the search dispatch (device_status) -- what its kernels flagged.
+    int close(int rc, int count, int wire, bool device_status, const char *what, std::initializer_list<hipStream_t> streams = {});
+};
+
+// ws_last_*_counts: the pair of the last call under `lease` to out, once that call is through; `none`: the refusal if no
+// call has run.
+int read_counts(ws_context *ctx, CountPair &c, ScratchLease &lease, const char *none, unsigned long long out[2]);
 
 } // namespace wsamd
 #pragma GCC visibility pop

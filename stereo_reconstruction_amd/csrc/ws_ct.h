@@ -49,7 +49,7 @@ struct CtMatchArgs {
 
 // The disparities a search looks at: what the geometry allows of the view's range (every pixel's candidates lie inside).
 // Left view d = 1 .. min(maxD, w1 - 1 - 2 half); right view d = minD .. min(maxD, w1) - 1.
-inline void census_range(const ws_params *p, const ws_image *L, int *d0, int *nd)
+inline void disparity_range(const ws_params *p, const ws_image *L, int *d0, int *nd)
 {
     const int half = (p->block_size - 1) / 2;
     if (p->view == WS_VIEW_LEFT) {
@@ -72,7 +72,7 @@ inline CtMatchArgs census_match_args(const ws_params *p, const ws_image *L, cons
     a.wide = p->cost == WS_COST_CENSUS_9X7;
     a.right = p->view == WS_VIEW_RIGHT;
     a.half = (p->block_size - 1) / 2;
-    census_range(p, L, &a.d0, &a.nd);
+    disparity_range(p, L, &a.d0, &a.nd);
     a.w = a.right ? R->width : L->width;
     a.h = a.right ? R->height : L->height;
     a.subpixel = p->subpixel != 0;

@@ -16,13 +16,8 @@ int check_lr(std::string *err, const ws_lr_params *lr)
     return WS_OK;
 }
 
-// the bytes [lo, hi) a map of h rows of w floats, `stride` floats apart, occupies
-struct Bytes {
-    uintptr_t lo, hi;
-    Bytes(const float *p, int w, int h, int stride)
-        : lo(reinterpret_cast<uintptr_t>(p)), hi(lo + ((size_t)(h - 1) * (size_t)stride + (size_t)w) * sizeof(float)) {}
-    bool overlaps(const Bytes &o) const { return lo < o.hi && o.lo < hi; }
-};
+// the bytes a map of h rows of w floats, `stride` floats apart, occupies
+Extent map_extent(const float *p, int w, int h, int stride) { return Extent(p, (size_t)stride * 4, (size_t)w * 4, (size_t)h); }
 
 // p run as the left view and as the right view, each checked as ws_search_host checks it, the left view first
 int view_params(std::string *err, const ws_params *p, const ws_image *L, const ws_image *R, ws_params q[2])
@@ -36,39 +31,13 @@ int view_params(std::string *err, const ws_params *p, const ws_image *L, const w
     return WS_OK;
 }
 
-// The context's check scratch on stream s: a check on another stream than the previous one first waits for it (on the
-// device).  release() marks the end of this one.
-int lr_acquire(ws_context *ctx, hipStream_t s)
-{
-    LrState &S = ctx->lr;
-    if (!S.ev) WS_HIP(&ctx->err, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-    if (S.busy && s != S.stream) WS_HIP(&ctx->err, hipStreamWaitEvent(s, S.ev, 0));
-    return WS_OK;
-}
-
-int lr_release(ws_context *ctx, hipStream_t s)
-{
-    LrState &S = ctx->lr;
-    S.busy = false;
-    S.ran = true;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    if (cap == hipStreamCaptureStatusNone) { // (an event recorded inside a capture cannot be waited for outside it)
-        WS_HIP(&ctx->err, hipEventRecord(S.ev, s));
-        S.busy = true;
-        S.stream = s;
-    }
-    return WS_OK;
-}
-
 // Zeroed counters, the check kernel, the fill if asked for, and the counts on their way to the host -- all on s.
 int enqueue_check(ws_context *ctx, LrMaps m, const ws_lr_params *lr, hipStream_t s)
 {
     LrState &S = ctx->lr;
     int rc;
     const size_t slot_bytes = lr_slot_words() * sizeof(unsigned long long);
-    if ((rc = ensure(&ctx->err, S.counts, slot_bytes + 2 * sizeof(unsigned long long))) != WS_OK) return rc;
-    WS_HIP(&ctx->err, host_ensure(S.counts_host, 2 * sizeof(unsigned long long)));
+    if ((rc = S.counts.reserve(&ctx->err, slot_bytes)) != WS_OK) return rc;
     m.state[0] = m.state[1] = nullptr;
     if (lr->fill == WS_LR_FILL_BACKGROUND) {
         const size_t n0 = ((size_t)lr_state_pitch(m.w[0]) * m.h[0] + 255) & ~(size_t)255;
@@ -76,12 +45,11 @@ int enqueue_check(ws_context *ctx, LrMaps m, const ws_lr_params *lr, hipStream_t
         m.state[0] = static_cast<uint8_t *>(S.states.p);
         m.state[1] = m.state[0] + n0;
     }
-    auto *slots = static_cast<unsigned long long *>(S.counts.p), *counts = slots + lr_slot_words();
+    auto *slots = static_cast<unsigned long long *>(S.counts.dev.p), *counts = slots + lr_slot_words();
     WS_HIP(&ctx->err, hipMemsetAsync(slots, 0, slot_bytes, s));
     WS_HIP(&ctx->err, launch_lr_check(m, lr->max_diff, slots, counts, s));
     if (lr->fill == WS_LR_FILL_BACKGROUND) WS_HIP(&ctx->err, launch_lr_fill(m, s));
-    WS_HIP(&ctx->err, hipMemcpyAsync(S.counts_host.p, counts, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    return WS_OK;
+    return S.counts.fetch(&ctx->err, counts, s);
 }
 
 LrMaps lr_maps(const float *l, int lw, int lh, int lstride, const float *r, int rw, int rh, int rstride, float *ol, int olstride,
@@ -110,14 +78,15 @@ int lr_maps_scratch(ws_context *ctx, size_t n_left, size_t n_right, int checked_
     return WS_OK;
 }
 
-// Both views on the device images into raw[0] (left map, dense) and raw[1] (right map, dense), one after the other on s:
-// they share the Searcher's scratch planes.
-int search_both(ws_context *ctx, const ws_params q[2], const ws_image *L, const ws_image *R, float *raw_left, float *raw_right,
-                hipStream_t s)
+// Both views on the device images into the dense maps at base + off[0] (left) and base + off[1] (right), one after the
+// other on s (they share the Searcher's scratch planes), then the check of the two into the maps m.out.
+int search_and_check(ws_context *ctx, const ws_params q[2], const ws_image *L, const ws_image *R, float *base, const size_t off[4],
+                     LrMaps m, const ws_lr_params *lr, hipStream_t s)
 {
-    if (const int rc = search(ctx->searcher, &ctx->err, &q[0], L, R, raw_left, L->width, nullptr, ctx->status_dev, s); rc != WS_OK)
-        return rc;
-    return search(ctx->searcher, &ctx->err, &q[1], L, R, raw_right, R->width, nullptr, ctx->status_dev, s);
+    int rc;
+    if ((rc = search(ctx->searcher, &ctx->err, &q[0], L, R, base + off[0], L->width, nullptr, ctx->status_dev, s)) != WS_OK) return rc;
+    if ((rc = search(ctx->searcher, &ctx->err, &q[1], L, R, base + off[1], R->width, nullptr, ctx->status_dev, s)) != WS_OK) return rc;
+    return enqueue_check(ctx, m, lr, s);
 }
 
 } // namespace
@@ -137,16 +106,15 @@ int ws_lr_check_device(ws_context *ctx, const float *left_dev, int lw, int lh, i
     if (!left_dev || !right_dev || !out_left_dev || !out_right_dev) return fail(&ctx->err, WS_ERR_ARG, "null map");
     if (lw < 1 || lh < 1 || rw < 1 || rh < 1 || lstride < lw || rstride < rw || out_lstride < lw || out_rstride < rw)
         return fail(&ctx->err, WS_ERR_ARG, "bad map size or stride");
-    const Bytes il(left_dev, lw, lh, lstride), ir(right_dev, rw, rh, rstride);
-    const Bytes ol(out_left_dev, lw, lh, out_lstride), orr(out_right_dev, rw, rh, out_rstride);
+    const Extent il = map_extent(left_dev, lw, lh, lstride), ir = map_extent(right_dev, rw, rh, rstride);
+    const Extent ol = map_extent(out_left_dev, lw, lh, out_lstride), orr = map_extent(out_right_dev, rw, rh, out_rstride);
     if (ol.overlaps(il) || ol.overlaps(ir) || orr.overlaps(il) || orr.overlaps(ir) || ol.overlaps(orr))
         return fail(&ctx->err, WS_ERR_ARG, "an output map overlaps an input map or the other output");
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    if ((rc = lr_acquire(ctx, s)) != WS_OK) return rc;
+    if ((rc = ctx->lr.lease.begin(&ctx->err, s)) != WS_OK) return rc;
     const LrMaps m = lr_maps(left_dev, lw, lh, lstride, right_dev, rw, rh, rstride, out_left_dev, out_lstride, out_right_dev, out_rstride);
-    if ((rc = enqueue_check(ctx, m, lr, s)) != WS_OK) return rc;
-    return lr_release(ctx, s);
+    return ctx->lr.lease.end(&ctx->err, s, enqueue_check(ctx, m, lr, s));
 }
 
 int ws_search_lr_device(ws_context *ctx, const ws_params *p, const ws_image *left_dev, const ws_image *right_dev,
@@ -161,18 +129,16 @@ int ws_search_lr_device(ws_context *ctx, const ws_params *p, const ws_image *lef
     const int lw = left_dev->width, lh = left_dev->height, rw = right_dev->width, rh = right_dev->height;
     if (!out_left_dev || !out_right_dev) return fail(&ctx->err, WS_ERR_ARG, "null output");
     if (out_lstride < lw || out_rstride < rw) return fail(&ctx->err, WS_ERR_ARG, "output stride below the map's width");
-    if (Bytes(out_left_dev, lw, lh, out_lstride).overlaps(Bytes(out_right_dev, rw, rh, out_rstride)))
+    if (map_extent(out_left_dev, lw, lh, out_lstride).overlaps(map_extent(out_right_dev, rw, rh, out_rstride)))
         return fail(&ctx->err, WS_ERR_ARG, "the output maps overlap");
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     float *base;
     size_t off[4];
     if ((rc = lr_maps_scratch(ctx, (size_t)lw * lh, (size_t)rw * rh, 0, &base, off)) != WS_OK) return rc;
-    if ((rc = lr_acquire(ctx, s)) != WS_OK) return rc;
-    if ((rc = search_both(ctx, q, left_dev, right_dev, base + off[0], base + off[1], s)) != WS_OK) return rc;
+    if ((rc = ctx->lr.lease.begin(&ctx->err, s)) != WS_OK) return rc;
     const LrMaps m = lr_maps(base + off[0], lw, lh, lw, base + off[1], rw, rh, rw, out_left_dev, out_lstride, out_right_dev, out_rstride);
-    if ((rc = enqueue_check(ctx, m, lr, s)) != WS_OK) return rc;
-    return lr_release(ctx, s);
+    return ctx->lr.lease.end(&ctx->err, s, search_and_check(ctx, q, left_dev, right_dev, base, off, m, lr, s));
 }
 
 // As ws_search_host, twice, with the images uploaded once: both views into context scratch, the check beside them, and
@@ -189,49 +155,34 @@ int ws_search_lr_host(ws_context *ctx, const ws_params *p, const ws_image *left,
     if (rc == WS_OK) rc = check_out(&ctx->err, &q[1], left, right, out_right, out_rstride, out_dtype, &owr, &ohr);
     if (rc != WS_OK) return rc;
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // the caller's buffers for the duration of the call (HostSpan, like ws_search_host)
-    HostSpan sp[4];
+    PairHostCall call(ctx, left, right);
+    HostSpan *sp = call.sp;
+    hipStream_t s = call.s;
     float *base;
     size_t off[4];
-    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left))) != WS_OK) return rc;
-    if ((rc = ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right))) != WS_OK) return rc;
+    if ((rc = call.open()) != WS_OK) return rc;
     if ((rc = lr_maps_scratch(ctx, (size_t)owl * ohl, (size_t)owr * ohr, 1, &base, off)) != WS_OK) return rc;
-    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    const int esz = out_elem_size(out_dtype);
     span_set(sp[2], out_left, (size_t)out_lstride * esz, (size_t)owl * esz, (size_t)ohl, &ctx->h_out);
     span_set(sp[3], out_right, (size_t)out_rstride * esz, (size_t)owr * esz, (size_t)ohr, &ctx->h_aux[0]);
     spans_attach(sp, 4);
     rc = [&]() -> int {
-        ws_image dl, dr;
-        WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
-        WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
         int r;
-        if ((r = lr_acquire(ctx, s)) != WS_OK) return r;
-        if ((r = search_both(ctx, q, &dl, &dr, base + off[0], base + off[1], s)) != WS_OK) return r;
+        if ((r = call.upload()) != WS_OK) return r;
+        if ((r = ctx->lr.lease.begin(&ctx->err, s)) != WS_OK) return r;
         const LrMaps m = lr_maps(base + off[0], owl, ohl, owl, base + off[1], owr, ohr, owr, base + off[2], owl, base + off[3], owr);
-        if ((r = enqueue_check(ctx, m, lr, s)) != WS_OK) return r;
-        if ((r = lr_release(ctx, s)) != WS_OK) return r;
+        if ((r = ctx->lr.lease.end(&ctx->err, s, search_and_check(ctx, q, &call.dl, &call.dr, base, off, m, lr, s))) != WS_OK) return r;
         WS_HIP(&ctx->err, span_download(sp[2], 0, (size_t)out_lstride, base + off[2], (size_t)owl, (size_t)ohl, kWireF32, esz, s));
         WS_HIP(&ctx->err, span_download(sp[3], 0, (size_t)out_rstride, base + off[3], (size_t)owr, (size_t)ohr, kWireF32, esz, s));
         return WS_OK;
     }();
-    for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
-    ctx->last_wire = kWireF32;
-    rc = finish_host_call(ctx, rc, sp, 4, {s}, "left-right host call");
-    return rc == WS_OK ? check_device_status(ctx) : rc;
+    return call.close(rc, 4, kWireF32, true, "left-right host call");
 }
 
 int ws_last_lr_counts(ws_context *ctx, unsigned long long counts[2])
 {
     if (!ctx || !counts) return WS_ERR_ARG;
-    LrState &S = ctx->lr;
-    if (!S.ran) return fail(&ctx->err, WS_ERR_ARG, "no left-right check has run on this context");
-    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
-    if (S.busy) WS_HIP(&ctx->err, hipEventSynchronize(S.ev));
-    const auto *c = reinterpret_cast<const unsigned long long *>(S.counts_host.p);
-    counts[0] = c[0];
-    counts[1] = c[1];
-    return WS_OK;
+    return read_counts(ctx, ctx->lr.counts, ctx->lr.lease, "no left-right check has run on this context", counts);
 }
 
 } // extern "C"

@@ -149,7 +149,8 @@ int run_canonical(Searcher &S, std::string *err, const ws_params *p, const ws_im
 int run_census(Searcher &S, std::string *err, const ws_params *p, const ws_image *L, const ws_image *R, float *out, int out_stride,
                hipStream_t s)
 {
-    const int ow = p->view == WS_VIEW_LEFT ? L->width : R->width, oh = p->view == WS_VIEW_LEFT ? L->height : R->height;
+    int ow, oh;
+    map_dims(p, L, R, &ow, &oh);
     if (out_stride < ow) return fail(err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
     const size_t esz = census_plane_elem(p->cost);
     int rc;
@@ -281,8 +282,7 @@ int check_params(std::string *err, const ws_params *p, const ws_image *L, const 
 int check_out(std::string *err, const ws_params *p, const ws_image *L, const ws_image *R, const void *out, int out_stride,
               int out_dtype, int *ow, int *oh)
 {
-    *ow = p->view == WS_VIEW_LEFT ? L->width : R->width;
-    *oh = p->view == WS_VIEW_LEFT ? L->height : R->height;
+    map_dims(p, L, R, ow, oh);
     if (!out || (out_dtype != WS_OUT_F32 && out_dtype != WS_OUT_F64)) return fail(err, WS_ERR_ARG, "bad output");
     if (out_stride < *ow) return fail(err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, *ow);
     return WS_OK;
@@ -342,22 +342,12 @@ int wire_for(const ws_params *p, const ws_image *L, const ws_image *R)
     return writes_only && fits ? kWireI16 : kWireF32;
 }
 
-// The Searcher's scratch planes are shared by every search: a search on another stream than the previous one first
-// waits (on the device) for that previous one to be done with them.
+// The Searcher's scratch planes are shared by every search, under the Searcher's lease.
 int search(Searcher &S, std::string *err, const ws_params *p, const ws_image *L, const ws_image *R, float *out,
            int out_stride, int16_t *out16, unsigned int *status, hipStream_t s)
 {
-    if (S.scratch_busy && s != S.scratch_stream) WS_HIP(err, hipStreamWaitEvent(s, S.ev_scratch, 0));
-    const int rc = search_on(S, err, p, L, R, out, out_stride, out16, status, s);
-    S.scratch_busy = false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    if (cap == hipStreamCaptureStatusNone) { // (an event recorded inside a capture cannot be waited for outside it)
-        WS_HIP(err, hipEventRecord(S.ev_scratch, s));
-        S.scratch_busy = true;
-        S.scratch_stream = s;
-    }
-    return rc;
+    if (const int rc = S.lease.begin(err, s); rc != WS_OK) return rc;
+    return S.lease.end(err, s, search_on(S, err, p, L, R, out, out_stride, out16, status, s));
 }
 
 } // namespace wsamd

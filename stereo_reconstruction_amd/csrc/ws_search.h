@@ -25,9 +25,7 @@ struct Searcher {
     int plan_next = 0; // the entry the next new problem replaces (round robin)
     const CachedPlan &plan_for(const Canon &c);
     int tune[3] = {0, 0, 0};              // ws_set_tuning: x-runs per tile, strip rows, threads (0 = automatic)
-    hipEvent_t ev_scratch = nullptr;      // end of the last search: the scratch planes are free again
-    hipStream_t scratch_stream = nullptr; // ... the stream it ran on
-    bool scratch_busy = false;
+    ScratchLease lease;                   // every search holds it: the scratch planes above are shared across streams
     bool profiling = false, kernel_timed = false; // ws_set_profiling; evk0 / evk1 bracket the last marching kernel
     hipEvent_t evk0 = nullptr, evk1 = nullptr;
     std::string last_kernel; // ws_last_launch_info

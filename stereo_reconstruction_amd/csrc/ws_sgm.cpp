@@ -13,20 +13,6 @@
 namespace wsamd {
 namespace {
 
-// The disparities an SGM search looks at: what the geometry allows of the view's range (the candidate sets of all
-// pixels lie inside it).  Left view d = 1 .. min(maxD, w1 - 1 - 2 half); right view d = minD .. min(maxD, w1) - 1.
-void disparity_range(const ws_params *p, const ws_image *L, int *d0, int *nd)
-{
-    const int half = (p->block_size - 1) / 2;
-    if (p->view == WS_VIEW_LEFT) {
-        *d0 = 1;
-        *nd = std::max(0, std::min(p->max_disparity, L->width - 1 - 2 * half));
-    } else {
-        *d0 = p->min_disparity;
-        *nd = p->max_disparity <= p->min_disparity ? 0 : std::max(0, std::min(p->max_disparity, L->width) - p->min_disparity);
-    }
-}
-
 // sgm_optional: the uniqueness calls, where a null sgm is the block route and only a given one is checked.
 int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R,
               bool sgm_optional = false)
@@ -44,16 +30,10 @@ int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, co
     int d0, nd;
     disparity_range(p, L, &d0, &nd);
     if (nd > kSgmMaxNd) return fail(err, WS_ERR_UNSUPPORTED, "SGM over %d disparities: at most %d", nd, kSgmMaxNd);
-    const int w = p->view == WS_VIEW_LEFT ? L->width : R->width, h = p->view == WS_VIEW_LEFT ? L->height : R->height;
+    int w, h;
+    map_dims(p, L, R, &w, &h);
     if ((long long)w * h >= (1LL << 31)) return fail(err, WS_ERR_UNSUPPORTED, "SGM on a map of 2^31 pixels or more");
     return WS_OK;
-}
-
-// Do two planes of `rows` rows (pitch and row length in bytes) share a byte of their extents?
-bool planes_overlap(const void *a, size_t a_pitch, size_t a_row, const void *b, size_t b_pitch, size_t b_row, size_t rows)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_pitch * (rows - 1) + a_row, b0 = (uintptr_t)b, b1 = b0 + b_pitch * (rows - 1) + b_row;
-    return a0 < b1 && b0 < a1;
 }
 
 int check_unique(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq, const ws_image *L,
@@ -77,8 +57,7 @@ Layout layout(const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, c
 {
     Layout y;
     disparity_range(p, L, &y.d0, &y.nd);
-    y.w = p->view == WS_VIEW_LEFT ? L->width : R->width;
-    y.h = p->view == WS_VIEW_LEFT ? L->height : R->height;
+    map_dims(p, L, R, &y.w, &y.h);
     const uint64_t cmax = sgm_cost_max(p->cost, p->block_size);
     y.cost16 = cmax <= 0xffffu;
     y.sum64 = sgm && (uint64_t)sgm->paths * (cmax + (uint64_t)sgm->p2) > 0xffffffffull;
@@ -114,38 +93,13 @@ int sgm_ensure(ws_context *ctx, size_t bytes)
     return WS_OK;
 }
 
-// The context's SGM scratch on stream s: a call on another stream than the previous one first waits for it (on the
-// device), as the left-right check does (ws_lr.cpp).
-int sgm_acquire(ws_context *ctx, hipStream_t s)
-{
-    SgmState &S = ctx->sgm;
-    if (!S.ev) WS_HIP(&ctx->err, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-    if (S.busy && s != S.stream) WS_HIP(&ctx->err, hipStreamWaitEvent(s, S.ev, 0));
-    return WS_OK;
-}
-
-int sgm_release(ws_context *ctx, hipStream_t s)
-{
-    SgmState &S = ctx->sgm;
-    S.busy = false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    if (cap == hipStreamCaptureStatusNone) { // (an event recorded inside a capture cannot be waited for outside it)
-        WS_HIP(&ctx->err, hipEventRecord(S.ev, s));
-        S.busy = true;
-        S.stream = s;
-    }
-    return WS_OK;
-}
-
 // Scratch, then the kernels on s into out (out_stride floats per row).  uq: the uniqueness winner instead (sgm may then
 // be null), with the confidence plane conf (or null) and the counts on their way to the host.
-int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
-                int out_stride, hipStream_t s, const ws_unique_params *uq = nullptr, float *conf = nullptr, int conf_stride = 0)
+int sgm_on(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
+           int out_stride, hipStream_t s, const ws_unique_params *uq, float *conf, int conf_stride)
 {
     const Layout y = layout(p, sgm, L, R);
     int rc;
-    if ((rc = sgm_acquire(ctx, s)) != WS_OK) return rc;
     // (a grown buffer is freed and allocated again: hipFree waits for the work still using the old one)
     if ((rc = sgm_ensure(ctx, y.bytes)) != WS_OK) return rc;
     SgmArgs a{};
@@ -175,22 +129,28 @@ int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, c
     a.out_pitch = out_stride;
     if (uq) {
         SgmState &S = ctx->sgm;
-        if ((rc = ensure(&ctx->err, S.counts, 2 * sizeof(unsigned long long))) != WS_OK) return rc;
-        WS_HIP(&ctx->err, host_ensure(S.counts_host, 2 * sizeof(unsigned long long)));
+        if ((rc = S.counts.reserve(&ctx->err, 0)) != WS_OK) return rc;
         UniqueArgs u{};
         u.ratio = uq->ratio;
         u.conf = conf;
         u.conf_pitch = conf_stride;
-        u.counts = static_cast<unsigned long long *>(S.counts.p);
+        u.counts = static_cast<unsigned long long *>(S.counts.dev.p);
         u.num_cus = ctx->num_cus;
-        WS_HIP(&ctx->err, hipMemsetAsync(u.counts, 0, 2 * sizeof(unsigned long long), s));
+        WS_HIP(&ctx->err, hipMemsetAsync(u.counts, 0, CountPair::kBytes, s));
         WS_HIP(&ctx->err, launch_unique(a, u, sgm ? sgm->paths : 0, s));
-        WS_HIP(&ctx->err, hipMemcpyAsync(S.counts_host.p, u.counts, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        S.unique_ran = true;
-    } else {
-        WS_HIP(&ctx->err, launch_sgm(a, sgm->paths, s));
+        return S.counts.fetch(&ctx->err, u.counts, s);
     }
-    return sgm_release(ctx, s);
+    WS_HIP(&ctx->err, launch_sgm(a, sgm->paths, s));
+    return WS_OK;
+}
+
+// ... under the lease of the context's SGM scratch (before the scratch is grown: the old one may still be in use)
+int enqueue_sgm(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
+                int out_stride, hipStream_t s, const ws_unique_params *uq = nullptr, float *conf = nullptr, int conf_stride = 0)
+{
+    ScratchLease &lease = ctx->sgm.lease;
+    if (const int rc = lease.begin(&ctx->err, s); rc != WS_OK) return rc;
+    return lease.end(&ctx->err, s, sgm_on(ctx, p, sgm, L, R, out, out_stride, s, uq, conf, conf_stride));
 }
 
 } // namespace
@@ -220,7 +180,8 @@ int ws_search_sgm_device(ws_context *ctx, const ws_params *p, const ws_sgm_param
     if (!ctx) return fail(nullptr, WS_ERR_ARG, "null context");
     int rc = check_sgm(&ctx->err, p, sgm, left_dev, right_dev);
     if (rc != WS_OK) return rc;
-    const int ow = p->view == WS_VIEW_LEFT ? left_dev->width : right_dev->width;
+    int ow, oh;
+    map_dims(p, left_dev, right_dev, &ow, &oh);
     if (!out_dev) return fail(&ctx->err, WS_ERR_ARG, "null output");
     if (out_stride < ow) return fail(&ctx->err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
@@ -239,26 +200,23 @@ int ws_search_sgm_host(ws_context *ctx, const ws_params *p, const ws_sgm_params 
     if (rc == WS_OK) rc = check_out(&ctx->err, p, left, right, out, out_stride, out_dtype, &ow, &oh);
     if (rc != WS_OK) return rc;
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    HostSpan sp[3];
-    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left))) != WS_OK) return rc;
-    if ((rc = ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right))) != WS_OK) return rc;
+    PairHostCall call(ctx, left, right);
+    HostSpan *sp = call.sp;
+    hipStream_t s = call.s;
+    if ((rc = call.open()) != WS_OK) return rc;
     if ((rc = ensure(&ctx->err, ctx->d_out, (size_t)ow * oh * sizeof(float))) != WS_OK) return rc;
-    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    const int esz = out_elem_size(out_dtype);
     span_set(sp[2], out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)oh, &ctx->h_out);
     spans_attach(sp, 3);
     rc = [&]() -> int {
-        ws_image dl, dr;
-        WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
-        WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
+        int r;
+        if ((r = call.upload()) != WS_OK) return r;
         float *map = static_cast<float *>(ctx->d_out.p);
-        if (const int r = enqueue_sgm(ctx, p, sgm, &dl, &dr, map, ow, s); r != WS_OK) return r;
+        if ((r = enqueue_sgm(ctx, p, sgm, &call.dl, &call.dr, map, ow, s)) != WS_OK) return r;
         WS_HIP(&ctx->err, span_download(sp[2], 0, (size_t)out_stride, map, (size_t)ow, (size_t)oh, kWireF32, esz, s));
         return WS_OK;
     }();
-    for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
-    ctx->last_wire = kWireF32;
-    return finish_host_call(ctx, rc, sp, 3, {s}, "SGM host call");
+    return call.close(rc, 3, kWireF32, false, "SGM host call");
 }
 
 int ws_validate_unique(const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq, const ws_image *left,
@@ -284,13 +242,14 @@ int ws_search_unique_device(ws_context *ctx, const ws_params *p, const ws_sgm_pa
     std::string *err = ctx ? &ctx->err : nullptr;
     int rc = check_unique(err, p, sgm, uq, left_dev, right_dev);
     if (rc != WS_OK) return rc;
-    const bool left = p->view == WS_VIEW_LEFT;
-    const int ow = left ? left_dev->width : right_dev->width, oh = left ? left_dev->height : right_dev->height;
+    int ow, oh;
+    map_dims(p, left_dev, right_dev, &ow, &oh);
     if (!out_dev) return fail(err, WS_ERR_ARG, "null output");
     if (out_stride < ow) return fail(err, WS_ERR_ARG, "out_stride %d < width %d", out_stride, ow);
     if (conf_dev) {
         if (conf_stride < ow) return fail(err, WS_ERR_ARG, "conf_stride %d < width %d", conf_stride, ow);
-        if (planes_overlap(out_dev, (size_t)out_stride * 4, (size_t)ow * 4, conf_dev, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh))
+        const Extent map(out_dev, (size_t)out_stride * 4, (size_t)ow * 4, (size_t)oh), cf(conf_dev, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh);
+        if (map.overlaps(cf))
             return fail(err, WS_ERR_ARG, "the confidence plane overlaps the map");
     }
     if (!ctx) return fail(nullptr, WS_ERR_ARG, "null context");
@@ -309,49 +268,40 @@ int ws_search_unique_host(ws_context *ctx, const ws_params *p, const ws_sgm_para
     int rc = check_unique(err, p, sgm, uq, left, right);
     if (rc == WS_OK) rc = check_out(err, p, left, right, out, out_stride, out_dtype, &ow, &oh);
     if (rc != WS_OK) return rc;
-    const int esz = out_dtype == WS_OUT_F32 ? 4 : 8;
+    const int esz = out_elem_size(out_dtype);
     if (conf) {
         if (conf_stride < ow) return fail(err, WS_ERR_ARG, "conf_stride %d < width %d", conf_stride, ow);
-        if (planes_overlap(out, (size_t)out_stride * esz, (size_t)ow * esz, conf, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh))
+        const Extent map(out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)oh), cf(conf, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh);
+        if (map.overlaps(cf))
             return fail(err, WS_ERR_ARG, "the confidence plane overlaps the map");
     }
     if (!ctx) return fail(nullptr, WS_ERR_ARG, "null context");
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     const size_t px = (size_t)ow * oh;
-    HostSpan sp[4];
-    if ((rc = ensure(&ctx->err, ctx->d_left, image_span(sp[0], left, &ctx->h_left))) != WS_OK) return rc;
-    if ((rc = ensure(&ctx->err, ctx->d_right, image_span(sp[1], right, &ctx->h_right))) != WS_OK) return rc;
+    PairHostCall call(ctx, left, right);
+    HostSpan *sp = call.sp;
+    hipStream_t s = call.s;
+    if ((rc = call.open()) != WS_OK) return rc;
     if ((rc = ensure(&ctx->err, ctx->d_out, (conf ? 2 : 1) * px * sizeof(float))) != WS_OK) return rc;
     span_set(sp[2], out, (size_t)out_stride * esz, (size_t)ow * esz, (size_t)oh, &ctx->h_out);
     if (conf) span_set(sp[3], conf, (size_t)conf_stride * 4, (size_t)ow * 4, (size_t)oh, &ctx->h_aux[0]);
     spans_attach(sp, 4);
     rc = [&]() -> int {
-        ws_image dl, dr;
-        WS_HIP(&ctx->err, upload_image(sp[0], left, static_cast<uint8_t *>(ctx->d_left.p), s, &dl));
-        WS_HIP(&ctx->err, upload_image(sp[1], right, static_cast<uint8_t *>(ctx->d_right.p), s, &dr));
+        int r;
+        if ((r = call.upload()) != WS_OK) return r;
         float *map = static_cast<float *>(ctx->d_out.p), *cmap = conf ? map + px : nullptr;
-        if (const int r = enqueue_sgm(ctx, p, sgm, &dl, &dr, map, ow, s, uq, cmap, ow); r != WS_OK) return r;
+        if ((r = enqueue_sgm(ctx, p, sgm, &call.dl, &call.dr, map, ow, s, uq, cmap, ow)) != WS_OK) return r;
         WS_HIP(&ctx->err, span_download(sp[2], 0, (size_t)out_stride, map, (size_t)ow, (size_t)oh, kWireF32, esz, s));
         if (conf) WS_HIP(&ctx->err, span_download(sp[3], 0, (size_t)conf_stride, cmap, (size_t)ow, (size_t)oh, kWireF32, 4, s));
         return WS_OK;
     }();
-    for (int i = 0; i < 3; ++i) ctx->last_how[i] = (int)sp[i].how;
-    ctx->last_wire = kWireF32;
-    return finish_host_call(ctx, rc, sp, 4, {s}, "uniqueness host call");
+    return call.close(rc, 4, kWireF32, false, "uniqueness host call");
 }
 
 int ws_last_unique_counts(ws_context *ctx, unsigned long long counts[2])
 {
     if (!ctx || !counts) return WS_ERR_ARG;
-    SgmState &S = ctx->sgm;
-    if (!S.unique_ran) return fail(&ctx->err, WS_ERR_ARG, "no uniqueness call has run on this context");
-    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
-    if (S.busy) WS_HIP(&ctx->err, hipEventSynchronize(S.ev));
-    const auto *c = reinterpret_cast<const unsigned long long *>(S.counts_host.p);
-    counts[0] = c[0];
-    counts[1] = c[1];
-    return WS_OK;
+    return read_counts(ctx, ctx->sgm.counts, ctx->sgm.lease, "no uniqueness call has run on this context", counts);
 }
 
 } // extern "C"

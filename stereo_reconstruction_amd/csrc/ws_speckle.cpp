@@ -1,5 +1,6 @@
 // ws_speckle.cpp -- the speckle filter of include/ws_stereo.h (extension): argument checks, the context's scratch for it
-// (SpeckleState), the launches of ws_speckle.hip, on device memory or on the caller's host map (through ws_staging.h).
+// (SpeckleState) under its lease, the launches of ws_speckle.hip, on device memory or on the caller's host map (through
+// ws_staging.h).
 #include "ws_context.h"
 
 #include <math.h>
@@ -27,41 +28,15 @@ int check_call(ws_context *ctx, const float *map, int w, int h, int stride, cons
     return WS_OK;
 }
 
-// The context's filter scratch on stream s, as lr_acquire / lr_release (ws_lr.cpp): a filter on another stream than the
-// previous one first waits for it (on the device); release() marks the end of this one.
-int speckle_acquire(ws_context *ctx, hipStream_t s)
-{
-    SpeckleState &S = ctx->speckle;
-    if (!S.ev) WS_HIP(&ctx->err, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-    if (S.busy && s != S.stream) WS_HIP(&ctx->err, hipStreamWaitEvent(s, S.ev, 0));
-    return WS_OK;
-}
-
-int speckle_release(ws_context *ctx, hipStream_t s)
-{
-    SpeckleState &S = ctx->speckle;
-    S.busy = false;
-    S.ran = true;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    if (cap == hipStreamCaptureStatusNone) { // (an event recorded inside a capture cannot be waited for outside it)
-        WS_HIP(&ctx->err, hipEventRecord(S.ev, s));
-        S.busy = true;
-        S.stream = s;
-    }
-    return WS_OK;
-}
-
 // Zeroed counters, the four kernels, and the counts on their way to the host -- all on s.
-int enqueue_filter(ws_context *ctx, float *map, int w, int h, int stride, const ws_speckle_params *sp, hipStream_t s)
+int filter_on(ws_context *ctx, float *map, int w, int h, int stride, const ws_speckle_params *sp, hipStream_t s)
 {
     SpeckleState &S = ctx->speckle;
     int rc;
     const size_t n = (size_t)w * h;
     const size_t slot_bytes = speckle_slot_words() * sizeof(unsigned long long);
     if ((rc = ensure(&ctx->err, S.planes, 4 * n * sizeof(int))) != WS_OK) return rc;
-    if ((rc = ensure(&ctx->err, S.counts, slot_bytes + 2 * sizeof(unsigned long long))) != WS_OK) return rc;
-    WS_HIP(&ctx->err, host_ensure(S.counts_host, 2 * sizeof(unsigned long long)));
+    if ((rc = S.counts.reserve(&ctx->err, slot_bytes)) != WS_OK) return rc;
     SpeckleArgs a{};
     a.map = map;
     a.w = w;
@@ -74,11 +49,18 @@ int enqueue_filter(ws_context *ctx, float *map, int w, int h, int stride, const 
     a.parent = a.label + n;
     a.count = a.parent + n;
     a.local = a.count + n;
-    auto *slots = static_cast<unsigned long long *>(S.counts.p), *counts = slots + speckle_slot_words();
+    auto *slots = static_cast<unsigned long long *>(S.counts.dev.p), *counts = slots + speckle_slot_words();
     WS_HIP(&ctx->err, hipMemsetAsync(slots, 0, slot_bytes, s));
     WS_HIP(&ctx->err, launch_speckle(a, slots, counts, s));
-    WS_HIP(&ctx->err, hipMemcpyAsync(S.counts_host.p, counts, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    return WS_OK;
+    return S.counts.fetch(&ctx->err, counts, s);
+}
+
+// ... under the filter's lease
+int enqueue_filter(ws_context *ctx, float *map, int w, int h, int stride, const ws_speckle_params *sp, hipStream_t s)
+{
+    ScratchLease &lease = ctx->speckle.lease;
+    if (const int rc = lease.begin(&ctx->err, s); rc != WS_OK) return rc;
+    return lease.end(&ctx->err, s, filter_on(ctx, map, w, h, stride, sp, s));
 }
 
 } // namespace
@@ -95,9 +77,7 @@ int ws_filter_speckles_device(ws_context *ctx, float *map_dev, int w, int h, int
     if (rc != WS_OK) return rc;
     WS_HIP(&ctx->err, hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    if ((rc = speckle_acquire(ctx, s)) != WS_OK) return rc;
-    if ((rc = enqueue_filter(ctx, map_dev, w, h, stride, sp, s)) != WS_OK) return rc;
-    return speckle_release(ctx, s);
+    return enqueue_filter(ctx, map_dev, w, h, stride, sp, s);
 }
 
 // The map goes up (dense), is filtered on the context's stream and comes back down into the caller's rows; the row
@@ -116,10 +96,7 @@ int ws_filter_speckles_host(ws_context *ctx, float *map, int w, int h, int strid
     spans_attach(sp1, 1);
     rc = [&]() -> int {
         WS_HIP(&ctx->err, span_upload_rows(sp1[0], 0, (size_t)stride * 4, dmap, (size_t)w * 4, (size_t)h, s));
-        int r;
-        if ((r = speckle_acquire(ctx, s)) != WS_OK) return r;
-        if ((r = enqueue_filter(ctx, dmap, w, h, w, sp, s)) != WS_OK) return r;
-        if ((r = speckle_release(ctx, s)) != WS_OK) return r;
+        if (const int r = enqueue_filter(ctx, dmap, w, h, w, sp, s); r != WS_OK) return r;
         WS_HIP(&ctx->err, span_download_bytes(sp1[0], 0, (size_t)stride * 4, dmap, (size_t)w * 4, (size_t)h, s));
         return WS_OK;
     }();
@@ -129,14 +106,7 @@ int ws_filter_speckles_host(ws_context *ctx, float *map, int w, int h, int strid
 int ws_last_speckle_counts(ws_context *ctx, unsigned long long counts[2])
 {
     if (!ctx || !counts) return WS_ERR_ARG;
-    SpeckleState &S = ctx->speckle;
-    if (!S.ran) return fail(&ctx->err, WS_ERR_ARG, "no speckle filter has run on this context");
-    WS_HIP(&ctx->err, hipSetDevice(ctx->device));
-    if (S.busy) WS_HIP(&ctx->err, hipEventSynchronize(S.ev));
-    const auto *c = reinterpret_cast<const unsigned long long *>(S.counts_host.p);
-    counts[0] = c[0];
-    counts[1] = c[1];
-    return WS_OK;
+    return read_counts(ctx, ctx->speckle.counts, ctx->speckle.lease, "no speckle filter has run on this context", counts);
 }
 
 } // extern "C"

@@ -51,7 +51,7 @@ def staircase_pair(w, h, lo, top, seed, view="left", noise=3, levels=None):
 
 
 def nd_of(view, block_size, min_disparity, max_disparity, w1):
-    """The number of disparities a search looks at (ws_sgm.cpp: disparity_range), restated."""
+    """The number of disparities a search looks at (ws_ct.h: disparity_range), restated."""
     half = (block_size - 1) // 2
     if view == "left":
         return max(0, min(max_disparity, w1 - 1 - 2 * half))

@@ -247,6 +247,46 @@ def test_search_lr_device_on_a_torch_stream(wslib, gpu_ctx, oracle):
     assert_bits(got_r, want_r, "host right")
 
 
+def scene_maps(rng, h, w):
+    """Integer disparity maps of a consistent scene (one disparity per 64-column block of a row; right(y, x - d) = d),
+    then a tenth of each map's pixels moved off by 3 .. 6: about a fifth of the pixels fail at max_diff 1."""
+    left = np.repeat(rng.integers(1, 9, size=(h, (w + 63) // 64)), 64, axis=1)[:, :w].astype(np.float32)
+    right = np.zeros((h, w), dtype=np.float32)
+    ys, xs = np.mgrid[0:h, 0:w]
+    p = xs - left.astype(np.int64)
+    right[ys[p >= 0], p[p >= 0]] = left[p >= 0]
+    for m in (left, right):
+        off = (rng.random(m.shape) < 0.1) & (m != 0)
+        m[off] += rng.integers(3, 7, size=int(off.sum())).astype(np.float32)
+    return left, right
+
+
+def test_two_streams_share_the_check_scratch_without_a_host_wait(wslib):
+    """A large check on stream A, at once a small one on stream B, then A again and B again, on one context with the
+    background fill (counters and state plane shared), the host waiting only at the end: each call's kernels must wait
+    for those of the call before it (the check's scratch lease).  A guard, not a proof: it cannot show that the wait
+    is there, only catch some ways of losing it."""
+    torch = _torch()
+    rng = np.random.default_rng(1024)
+    a, b = scene_maps(rng, 512, 1024), scene_maps(rng, 40, 96)
+    want_a, want_b = lr_check(*a, 1.0, True), lr_check(*b, 1.0, True)
+    assert 0.1 < want_a[2][0] / a[0].size < 0.3 and 0.1 < want_a[2][1] / a[1].size < 0.3, want_a[2]
+    with wslib.WindowSearch(0) as ctx:
+        sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+        ta, tb = (tuple(torch.from_numpy(x).cuda() for x in m) for m in (a, b))
+        calls = [(t, want, s, tuple(torch.full_like(x, float("nan")) for x in t))
+                 for t, want, s in ((ta, want_a, sa), (tb, want_b, sb), (ta, want_a, sa), (tb, want_b, sb))]
+        torch.cuda.synchronize()                 # the maps and the NaN outputs are in place; from here on no host wait
+        for t, _, s, outs in calls:
+            ctx.lr_check_device(*t, *outs, 1.0, True, stream=s.cuda_stream)
+        counts = ctx.last_lr_counts()            # (waits for the last check alone)
+        torch.cuda.synchronize()
+        assert counts == want_b[2]
+        for (_, want, _, outs), what in zip(calls, ("A", "B", "A again", "B again")):
+            assert_bits(outs[0].cpu().numpy(), want[0], (what, "left"))
+            assert_bits(outs[1].cpu().numpy(), want[1], (what, "right"))
+
+
 def test_the_cxx_facade_returns_the_checked_maps(wslib, gpu_ctx, oracle, tmp_path):
     left, right, _ = make_pair(140, 50, 20, seed=9, right_width=130)
     exe = str(tmp_path / "lr_driver")

@@ -202,7 +202,7 @@ def enqueue(wslib, ctx, keep, L, R, args, stream):
 
 def test_two_streams_share_the_scratch_without_a_host_wait(wslib):
     """Stream A, at once a different search on stream B, then A again, on one context, the host waiting only at the
-    end: B's kernels must wait for A's (sgm_acquire), A's second call for B's."""
+    end: B's kernels must wait for A's (the lease of the SGM scratch), A's second call for B's."""
     torch = _torch()
     La, Ra, a_args, a_want = long_call()
     Lb, Rb, b_args, b_want, c_args, c_want = other_calls()

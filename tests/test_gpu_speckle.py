@@ -222,6 +222,28 @@ def test_orders_behind_search_lr_device_on_a_stream(wslib, gpu_ctx, oracle):
             assert bool((ol.as_strided((150, 409), (409, 1))[:, 400:] == -5.0).all())
 
 
+def test_two_streams_share_the_filter_scratch_without_a_host_wait(wslib):
+    """A large map filtered on stream A, at once a small one on stream B, then copies of both again, on one context,
+    the host waiting only at the end: each filter's kernels must wait for those of the filter before it (the
+    filter's scratch lease: the four planes and the counters are shared).  A guard, not a proof: it cannot show that
+    the wait is there, only catch some ways of losing it."""
+    torch = _torch()
+    rng = np.random.default_rng(512)
+    a, b = random_map(rng, 512, 1024, levels=4, special=0.1), random_map(rng, 40, 96, levels=3, special=0.15)
+    want_a, want_b = filter_speckles(a, 0.0, 30, 1.0), filter_speckles(b, 0.0, 30, 1.0)
+    with wslib.WindowSearch(0) as ctx:
+        sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+        calls = [(torch.from_numpy(m).cuda(), want, s) for m, want, s in ((a, want_a, sa), (b, want_b, sb), (a, want_a, sa), (b, want_b, sb))]
+        torch.cuda.synchronize()                 # the maps are in place; from here on no host wait
+        for t, _, s in calls:
+            ctx.filter_speckles_device(t, 0.0, 30, 1.0, stream=s.cuda_stream)
+        counts = ctx.last_speckle_counts()       # (waits for the last filter alone)
+        torch.cuda.synchronize()
+        assert counts == want_b[1]
+        for (t, want, _), what in zip(calls, ("A", "B", "A again", "B again")):
+            assert_bits(t.cpu().numpy(), want[0], what)
+
+
 def test_the_cxx_facade_filters_in_place(wslib, gpu_ctx, tmp_path):
     exe = str(tmp_path / "speckle_driver")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", ROOT, "-o", exe, os.path.join(ROOT, "tests", "cxx", "speckle_driver.cpp"),
