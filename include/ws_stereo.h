@@ -393,6 +393,51 @@ int ws_search_unique_host(ws_context *ctx, const ws_params *p, const ws_sgm_para
 /* {failed nodes, nodes} of the last uniqueness call of this context; waits for that call's stream. */
 int ws_last_unique_counts(ws_context *ctx, unsigned long long counts[2]);
 
+/* ---- both views from one volume (extension) ------------------------------------------------- */
+/*
+ * Both views' maps, and their left-right check, from the sums of ONE view: S(p, d) of the base view already holds a
+ * cost for every pair (left column, right column) of a row, so the other view's map is the minimum of the same sums
+ * read along the diagonal x -+ d (Hirschmueller; OpenCV's disp2 / disp12MaxDiff).  p, K(p), C, nodes, S and the
+ * fallbacks are those of the SGM and uniqueness sections.  p->view names the BASE VIEW.  sgm may be NULL: S = C, the
+ * uniqueness calls' block route.
+ *   1. Base map: what the library already computes, bit for bit, the sub-pixel map included.  With uq given it is
+ *      ws_search_unique_*'s map; with sgm given and uq NULL, ws_search_sgm_*'s; with both NULL, ws_search_*'s at
+ *      smoothFactor 1.
+ *   2. Derived map, base LEFT (d = 1 + j): w2 x h2, in the right view's convention.  The candidates of (y, x_r) are the d
+ *      for which x = x_r + d < w1, (y, x) is a node of the base view and d is in K(y, x).  The value is the d that
+ *      minimises S((y, x_r + d), d); ties take the smallest d.  It is stored as (float)d.
+ *   3. Derived map, base RIGHT (d = minD + j): w1 x h1, in the left view's convention.  The candidates of (y, x_l) are the
+ *      d for which 0 <= x = x_l - d < w2, (y, x) is a node and d is in K(y, x); ties take the largest d.
+ *   4. No candidate: a derived pixel without candidates stores 0.0f ("no disparity"), every row beyond the base map's
+ *      rows included.  With base RIGHT and minD = 0 a winner d = 0 also stores 0.0f, as the direct right map does.  The
+ *      check's rule 1 reads both as empty.
+ *   5. The derived map is integer-valued: it does not depend on p->subpixel, nor on uq -- every node's sums take part,
+ *      whether or not the base pixel fails the ratio test.
+ *   6. The check: with lr given, the two outputs are exactly what ws_lr_check_device makes of the two raw maps (base and
+ *      derived, each in its own view's slot), and ws_last_lr_counts reports that check's counts.  With uq given,
+ *      ws_last_unique_counts reports the base winner's counts.  With lr NULL the outputs are the raw maps.
+ *   7. Identity: sgm == NULL and sgm = {paths, 0, 0} give the same two maps (S = paths * C).
+ *   8. Refusals, without a device: everything ws_validate_unique refuses, with uq allowed to be NULL; what the left-right
+ *      check refuses of lr, when lr is given; WS_ERR_ARG for a null output, a stride below its map's width, or
+ *      overlapping outputs.
+ * The derived map is not the other view's searched map: its windows are the base view's, so the two differ on some
+ * pixels.  out_left is always w1 x h1 and out_right always w2 x h2, whichever view is the base.  The volumes and both
+ * winners use the SGM calls' scratch, the raw maps and the check the left-right check's; a call takes the two leases in
+ * that order.  The sgm == NULL route writes the whole cost plane: for the plain block search ws_search_lr_* (two
+ * marching searches) stays the fast route.
+ */
+int ws_validate_pair(const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq, const ws_lr_params *lr,
+                     const ws_image *left, const ws_image *right);
+/* On device images into two float32 device maps (strides in floats).  Only enqueues, on `stream` (NULL = the context's own). */
+int ws_search_pair_device(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq,
+                          const ws_lr_params *lr, const ws_image *left_dev, const ws_image *right_dev, float *out_left_dev,
+                          int out_lstride, float *out_right_dev, int out_rstride, void *stream);
+/* On host buffers, synchronous, as ws_search_lr_host: the images go up once, both maps come down as out_dtype (F64: the
+ * float32 map widened).  Strides in elements. */
+int ws_search_pair_host(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq,
+                        const ws_lr_params *lr, const ws_image *left, const ws_image *right, void *out_left, int out_lstride,
+                        void *out_right, int out_rstride, int out_dtype);
+
 /* ---- census-transform matching cost (extension) -------------------------------------------- */
 /*
  * WS_COST_CENSUS_5X5 / WS_COST_CENSUS_9X7 as ws_params.cost: the block search, and semi-global matching over it, on a

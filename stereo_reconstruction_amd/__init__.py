@@ -52,7 +52,7 @@ EXPORTS = ["ws_version", "ws_params_default", "ws_create", "ws_destroy", "ws_las
            "ws_filter_speckles_device", "ws_filter_speckles_host", "ws_last_speckle_counts",
            "ws_validate_sgm", "ws_sgm_scratch_bytes", "ws_search_sgm_device", "ws_search_sgm_host",
            "ws_validate_unique", "ws_unique_scratch_bytes", "ws_search_unique_device", "ws_search_unique_host",
-           "ws_last_unique_counts",
+           "ws_last_unique_counts", "ws_validate_pair", "ws_search_pair_device", "ws_search_pair_host",
            "ws_census_transform_device", "ws_census_transform_host"]
 JOB_NOT_RUN = 1  # ws_job.status of a job its worker never reached (WS_JOB_NOT_RUN)
 
@@ -182,6 +182,18 @@ def unique_scratch_bytes(params, left, right, sgm=None):
     if rc != 0:
         raise WsError(rc, lib.ws_last_error(None).decode())
     return int(n.value)
+
+
+def validate_pair(params, left, right, sgm=None, ratio=None, max_diff=None, fill=False):
+    """ws_validate_pair on host images: 0 or the WS_ERR_* status a pair call would return.  ratio None: no uniqueness
+    test; max_diff None: no left-right check."""
+    lib = load_library()
+    sp, spp = _sgm_or_null(sgm)
+    uq = None if ratio is None else unique_params(ratio)
+    lr = None if max_diff is None else lr_params(max_diff, fill)
+    return int(lib.ws_validate_pair(ctypes.byref(params), spp, None if uq is None else ctypes.byref(uq),
+                                    None if lr is None else ctypes.byref(lr), ctypes.byref(_image_struct(left)),
+                                    ctypes.byref(_image_struct(right))))
 
 
 class _Job(ctypes.Structure):
@@ -316,6 +328,11 @@ def load_library(build_if_missing=False):
     lib.ws_search_unique_host.argtypes = [vp, P(_Params), P(_SgmParams), P(_UniqueParams), P(_Image), P(_Image), vp, ci, ci,
                                           vp, ci]
     lib.ws_last_unique_counts.argtypes = [vp, P(ctypes.c_ulonglong)]
+    lib.ws_validate_pair.argtypes = [P(_Params), P(_SgmParams), P(_UniqueParams), P(_LrParams), P(_Image), P(_Image)]
+    lib.ws_search_pair_device.argtypes = [vp, P(_Params), P(_SgmParams), P(_UniqueParams), P(_LrParams), P(_Image), P(_Image),
+                                          vp, ci, vp, ci, vp]
+    lib.ws_search_pair_host.argtypes = [vp, P(_Params), P(_SgmParams), P(_UniqueParams), P(_LrParams), P(_Image), P(_Image),
+                                        vp, ci, vp, ci, ci]
     lib.ws_census_transform_device.argtypes = [vp, P(_Image), ci, vp, ci, vp]
     lib.ws_census_transform_host.argtypes = [vp, P(_Image), ci, vp, ci]
     _lib = lib
@@ -549,6 +566,40 @@ class WindowSearch:
         c = (ctypes.c_ulonglong * 2)()
         self._check(self._lib.ws_last_unique_counts(self._h, c))
         return int(c[0]), int(c[1])
+
+    # -- both views from one volume (extension; rules in include/ws_stereo.h) ---------------------
+    def search_pair(self, params, left, right, sgm=None, ratio=None, max_diff=None, fill=False, dtype=np.float64):
+        """ws_search_pair_host: the base view's map (params.view; as search_sgm / search_unique / search compute it)
+        and the other view's map derived from the same sums, as (left_map, right_map).  sgm: None for the block
+        search's costs or (paths, p1, p2); ratio: None or the uniqueness ratio of the base winner; max_diff: None for
+        the raw maps, else the two are left-right checked (fill as for search_lr)."""
+        La, Li = _host_image(left)
+        Ra, Ri = _host_image(right)
+        if dtype not in (np.float32, np.float64):
+            raise ValueError("dtype must be float32 or float64")
+        outl = np.empty(La.shape[:2], dtype=dtype)
+        outr = np.empty(Ra.shape[:2], dtype=dtype)
+        sp, spp = _sgm_or_null(sgm)
+        uq = None if ratio is None else unique_params(ratio)
+        lr = None if max_diff is None else lr_params(max_diff, fill)
+        self._check(self._lib.ws_search_pair_host(
+            self._h, ctypes.byref(params), spp, None if uq is None else ctypes.byref(uq),
+            None if lr is None else ctypes.byref(lr), ctypes.byref(Li), ctypes.byref(Ri), outl.ctypes.data, outl.shape[1],
+            outr.ctypes.data, outr.shape[1], OUT_F64 if dtype == np.float64 else OUT_F32))
+        return outl, outr
+
+    def search_pair_device(self, params, left_t, right_t, out_left_t, out_right_t, sgm=None, ratio=None, max_diff=None,
+                           fill=False, stream=None):
+        """ws_search_pair_device on uint8 CUDA images and two float32 CUDA maps (rows may be padded).  Only enqueues."""
+        Li = _Image(left_t.data_ptr(), left_t.shape[1], left_t.shape[0], left_t.stride(0))
+        Ri = _Image(right_t.data_ptr(), right_t.shape[1], right_t.shape[0], right_t.stride(0))
+        sp, spp = _sgm_or_null(sgm)
+        uq = None if ratio is None else unique_params(ratio)
+        lr = None if max_diff is None else lr_params(max_diff, fill)
+        self._check(self._lib.ws_search_pair_device(
+            self._h, ctypes.byref(params), spp, None if uq is None else ctypes.byref(uq),
+            None if lr is None else ctypes.byref(lr), ctypes.byref(Li), ctypes.byref(Ri), out_left_t.data_ptr(),
+            out_left_t.stride(0), out_right_t.data_ptr(), out_right_t.stride(0), ctypes.c_void_p(stream or 0)))
 
     # -- census transform (extension; rules in include/ws_stereo.h) -------------------------------
     def census_transform(self, img, cost):
@@ -952,6 +1003,17 @@ class BlockSearch:
         p = make_params(VIEW_LEFT, self.blockSize_, self.minDisparity_, self.maxDisparity_,
                         smoothFactor, self.cost, varBlock, thres, self.subpixel)
         return _ctx(self._context).search_lr(p, self.leftImage_, self.rightImage_, maxDiff, fill)
+
+    def computeDisparityMapsCheckedSGM(self, P1, P2, paths=8, maxDiff=1.0, fill=False, uniquenessRatio=None, base="left"):
+        """Extension: semi-global matching of the `base` view, the other view's map derived from the same sums, and
+        the left-right check of the two (disp12MaxDiff = maxDiff) in one call.  Returns (left_map, right_map) as
+        float64; failed pixels are 0 or filled.  uniquenessRatio: None, or the ratio test on the base winner."""
+        if base not in ("left", "right"):
+            raise ValueError("base must be 'left' or 'right'")
+        p = make_params(VIEW_LEFT if base == "left" else VIEW_RIGHT, self.blockSize_, self.minDisparity_,
+                        self.maxDisparity_, 1.0, self.cost, subpixel=self.subpixel)
+        return _ctx(self._context).search_pair(p, self.leftImage_, self.rightImage_, (paths, P1, P2), uniquenessRatio,
+                                               maxDiff, fill)
 
 
 class LinearSearch:

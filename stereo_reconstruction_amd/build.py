@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libws_stereo.so")
 SOURCES = ["ws_march.hip", "ws_march_nd4.hip", "ws_march_mfma.hip", "ws_prepass.hip", "ws_border.hip", "ws_smooth.hip", "ws_consumers.hip", "ws_rectify.hip", "ws_mesh.hip",
-           "ws_lr.hip", "ws_speckle.hip", "ws_sgm.hip", "ws_ct.hip", "ws_capi.cpp", "ws_lr.cpp", "ws_speckle.cpp", "ws_sgm.cpp", "ws_search.cpp",
+           "ws_lr.hip", "ws_speckle.hip", "ws_sgm.hip", "ws_ct.hip", "ws_capi.cpp", "ws_lr.cpp", "ws_speckle.cpp", "ws_sgm.cpp", "ws_pair.cpp", "ws_search.cpp",
            "ws_staging.cpp", "ws_io.cpp", "ws_batch.cpp"]
 HEADERS = [os.path.join(CSRC, "ws_kernels.h"), os.path.join(CSRC, "ws_device.h"), os.path.join(CSRC, "ws_march_kernel.h"), os.path.join(CSRC, "ws_march_mfma.h"), os.path.join(CSRC, "ws_march_plan.h"),
            os.path.join(CSRC, "ws_rectify.h"), os.path.join(CSRC, "ws_batch_core.h"), os.path.join(CSRC, "ws_capi_internal.h"), os.path.join(CSRC, "ws_context.h"),
@@ -67,7 +67,7 @@ def build(force=False, verbose=False):
                 cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
             jobs.append((subprocess.Popen(cmd), obj))
     failed = False
-    for proc, obj in jobs:  # (at most len(SOURCES) = 21 compilers at once)
+    for proc, obj in jobs:  # (at most len(SOURCES) = 22 compilers at once)
         tmp_o = obj + ".tmp.%d" % os.getpid()
         if proc.wait() == 0:
             os.replace(tmp_o, obj)

@@ -142,6 +142,16 @@ struct PairHostCall {
     int close(int rc, int count, int wire, bool device_status, const char *what, std::initializer_list<hipStream_t> streams = {});
 };
 
+// What ws_lr.cpp shares with ws_pair.cpp, all under the context's left-right lease.  check_lr: the refusals of a
+// ws_lr_params.  lr_maps: two maps in, two out, strides in floats.  lr_maps_scratch: LrState::raw as both raw maps
+// (dense), then (checked_too) both checked maps; offsets in floats.  enqueue_check: zeroed counters, the check kernel,
+// the fill if asked for, and the counts on their way to the host, all on s.
+int check_lr(std::string *err, const ws_lr_params *lr);
+LrMaps lr_maps(const float *l, int lw, int lh, int lstride, const float *r, int rw, int rh, int rstride, float *ol, int olstride,
+               float *orr, int orstride);
+int lr_maps_scratch(ws_context *ctx, size_t n_left, size_t n_right, int checked_too, float **base, size_t off[4]);
+int enqueue_check(ws_context *ctx, LrMaps m, const ws_lr_params *lr, hipStream_t s);
+
 // ws_last_*_counts: the pair of the last call under `lease` to out, once that call is through; `none`: the refusal if no
 // call has run.
 int read_counts(ws_context *ctx, CountPair &c, ScratchLease &lease, const char *none, unsigned long long out[2]);

@@ -6,7 +6,6 @@
 #include <stdint.h>
 
 namespace wsamd {
-namespace {
 
 int check_lr(std::string *err, const ws_lr_params *lr)
 {
@@ -15,6 +14,8 @@ int check_lr(std::string *err, const ws_lr_params *lr)
     if (lr->fill != WS_LR_FILL_NONE && lr->fill != WS_LR_FILL_BACKGROUND) return fail(err, WS_ERR_ARG, "unknown fill %d", lr->fill);
     return WS_OK;
 }
+
+namespace {
 
 // the bytes a map of h rows of w floats, `stride` floats apart, occupies
 Extent map_extent(const float *p, int w, int h, int stride) { return Extent(p, (size_t)stride * 4, (size_t)w * 4, (size_t)h); }
@@ -30,6 +31,8 @@ int view_params(std::string *err, const ws_params *p, const ws_image *L, const w
     }
     return WS_OK;
 }
+
+} // namespace
 
 // Zeroed counters, the check kernel, the fill if asked for, and the counts on their way to the host -- all on s.
 int enqueue_check(ws_context *ctx, LrMaps m, const ws_lr_params *lr, hipStream_t s)
@@ -77,6 +80,8 @@ int lr_maps_scratch(ws_context *ctx, size_t n_left, size_t n_right, int checked_
     *base = static_cast<float *>(ctx->lr.raw.p);
     return WS_OK;
 }
+
+namespace {
 
 // Both views on the device images into the dense maps at base + off[0] (left) and base + off[1] (right), one after the
 // other on s (they share the Searcher's scratch planes), then the check of the two into the maps m.out.

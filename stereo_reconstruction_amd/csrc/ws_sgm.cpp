@@ -11,11 +11,8 @@
 #include <algorithm>
 
 namespace wsamd {
-namespace {
 
-// sgm_optional: the uniqueness calls, where a null sgm is the block route and only a given one is checked.
-int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R,
-              bool sgm_optional = false)
+int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, bool sgm_optional)
 {
     if (const int rc = check_params(err, p, L, R); rc != WS_OK) return rc;
     if (p->view == WS_VIEW_LINEAR) return fail(err, WS_ERR_UNSUPPORTED, "SGM on LinearSearch");
@@ -36,13 +33,20 @@ int check_sgm(std::string *err, const ws_params *p, const ws_sgm_params *sgm, co
     return WS_OK;
 }
 
+int check_ratio(std::string *err, const ws_unique_params *uq)
+{
+    if (uq->ratio < 0 || uq->ratio > 100) return fail(err, WS_ERR_ARG, "ratio %d: must be 0 .. 100", uq->ratio);
+    return WS_OK;
+}
+
+namespace {
+
 int check_unique(std::string *err, const ws_params *p, const ws_sgm_params *sgm, const ws_unique_params *uq, const ws_image *L,
                  const ws_image *R)
 {
     if (const int rc = check_sgm(err, p, sgm, L, R, true); rc != WS_OK) return rc;
     if (!uq) return fail(err, WS_ERR_ARG, "null ws_unique_params");
-    if (uq->ratio < 0 || uq->ratio > 100) return fail(err, WS_ERR_ARG, "ratio %d: must be 0 .. 100", uq->ratio);
-    return WS_OK;
+    return check_ratio(err, uq);
 }
 
 // The scratch of one call: the candidate intervals, the cost plane and the sums (none without sgm: the uniqueness calls'
@@ -93,15 +97,14 @@ int sgm_ensure(ws_context *ctx, size_t bytes)
     return WS_OK;
 }
 
-// Scratch, then the kernels on s into out (out_stride floats per row).  uq: the uniqueness winner instead (sgm may then
-// be null), with the confidence plane conf (or null) and the counts on their way to the host.
-int sgm_on(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
-           int out_stride, hipStream_t s, const ws_unique_params *uq, float *conf, int conf_stride)
+} // namespace
+
+int sgm_prepare(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
+                int out_stride, hipStream_t s, SgmArgs *args)
 {
     const Layout y = layout(p, sgm, L, R);
-    int rc;
     // (a grown buffer is freed and allocated again: hipFree waits for the work still using the old one)
-    if ((rc = sgm_ensure(ctx, y.bytes)) != WS_OK) return rc;
+    if (const int rc = sgm_ensure(ctx, y.bytes); rc != WS_OK) return rc;
     SgmArgs a{};
     a.L = L->data; a.R = R->data;
     a.w1 = L->width; a.h1 = L->height; a.s1 = L->stride;
@@ -127,9 +130,16 @@ int sgm_on(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const 
     a.subpixel = p->subpixel != 0;
     a.out = out;
     a.out_pitch = out_stride;
+    *args = a;
+    return WS_OK;
+}
+
+int sgm_winner(ws_context *ctx, const SgmArgs &a, const ws_sgm_params *sgm, const ws_unique_params *uq, float *conf, int conf_stride,
+               hipStream_t s)
+{
     if (uq) {
         SgmState &S = ctx->sgm;
-        if ((rc = S.counts.reserve(&ctx->err, 0)) != WS_OK) return rc;
+        if (const int rc = S.counts.reserve(&ctx->err, 0); rc != WS_OK) return rc;
         UniqueArgs u{};
         u.ratio = uq->ratio;
         u.conf = conf;
@@ -140,8 +150,20 @@ int sgm_on(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const 
         WS_HIP(&ctx->err, launch_unique(a, u, sgm ? sgm->paths : 0, s));
         return S.counts.fetch(&ctx->err, u.counts, s);
     }
-    WS_HIP(&ctx->err, launch_sgm(a, sgm->paths, s));
+    WS_HIP(&ctx->err, launch_sgm(a, sgm ? sgm->paths : 0, s));
     return WS_OK;
+}
+
+namespace {
+
+// Scratch, then the kernels on s into out (out_stride floats per row).  uq: the uniqueness winner instead (sgm may then
+// be null), with the confidence plane conf (or null) and the counts on their way to the host.
+int sgm_on(ws_context *ctx, const ws_params *p, const ws_sgm_params *sgm, const ws_image *L, const ws_image *R, float *out,
+           int out_stride, hipStream_t s, const ws_unique_params *uq, float *conf, int conf_stride)
+{
+    SgmArgs a;
+    if (const int rc = sgm_prepare(ctx, p, sgm, L, R, out, out_stride, s, &a); rc != WS_OK) return rc;
+    return sgm_winner(ctx, a, sgm, uq, conf, conf_stride, s);
 }
 
 // ... under the lease of the context's SGM scratch (before the scratch is grown: the old one may still be in use)

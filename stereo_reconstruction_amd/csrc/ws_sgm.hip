@@ -16,6 +16,9 @@
 //   * ws_unique_wta_kernel: that winner with the uniqueness test and the confidence of include/ws_stereo.h, on S or
 //     (block route, no path kernel) on C itself.  Each lane keeps its best key and its runner-up's value, so the curve
 //     is read once: the rival minimum m2 is a second wave minimum over what the lanes still hold.
+//   * ws_pair_wta_kernel: the other view's map from the same volume ("both views from one volume").  One workgroup per
+//     row and span of kPairSpan derived columns; a 64-bit LDS slot per derived column takes the minimum of the packed
+//     keys (S, tie tag) that the base pixels' curves offer along the diagonal.
 // Every store is a plain vector store.
 #include "ws_sgm.h"
 #include "ws_ct.h"
@@ -34,6 +37,7 @@ constexpr int kSgmCols = kSgmTile + 2 * kSgmMaxHalf; // column sums a tile needs
 constexpr int kSgmColsPerWave = (kSgmCols + 3) / 4;
 constexpr uint32_t kNoCandidate = 0xffffffffu;
 constexpr int kUniqueBlocksPerCu = 8;                // uniqueness winner: 32 waves per CU, all resident
+constexpr int kPairUnroll = 4;                       // diagonal winner: base columns a wave has in flight per trip
 static_assert(kSgmThreads == 256 && kSgmTile == 64, "four waves, 16 output columns each");
 static_assert(kSgmMaxNd <= 64 * 32 && kSgmMaxNd < 4096, "32 disparities per lane; 12-bit tie tags");
 
@@ -272,12 +276,12 @@ __global__ __launch_bounds__(kSgmThreads) void ws_sgm_path_kernel(SgmArgs a, int
     }
 }
 
+// ST: S as uint32_t / unsigned long long; the pair call's block route reads C (uint16_t / uint32_t) through it instead.
 template <typename ST>
-__global__ __launch_bounds__(kSgmThreads) void ws_sgm_wta_kernel(SgmArgs a)
+__global__ __launch_bounds__(kSgmThreads) void ws_sgm_wta_kernel(SgmArgs a, const ST *sum)
 {
     const int lane = threadIdx.x & 63;
     const long long n = (long long)a.w * a.h;
-    const ST *sum = static_cast<const ST *>(a.sum);
     const long long waves = (long long)gridDim.x * (kSgmThreads / 64);
     for (long long i = (long long)blockIdx.x * (kSgmThreads / 64) + (threadIdx.x >> 6); i < n; i += waves) {
         const int y = (int)(i / a.w), x = (int)(i % a.w);
@@ -382,6 +386,75 @@ __global__ __launch_bounds__(kSgmThreads) void ws_unique_wta_kernel(SgmArgs a, c
     }
 }
 
+// The derived map of the pair call (include/ws_stereo.h, "both views from one volume").  The base view's pixel (y, x)
+// offers vol(y, x, j) to the derived column c = x - d (base LEFT) or x + d (base RIGHT), d = d0 + j: the 64 entries a wave
+// loads from one curve are contiguous and go to 64 different, consecutive slots.  Workgroup (y, span) owns the derived
+// columns [c0, c0 + kPairSpan) of row y and visits the base columns that reach them, each for the part of its interval
+// [lo, hi) that falls into the span, so every entry of the volume is read once over the grid.  A wave takes kPairUnroll
+// neighbouring base columns per trip and issues their loads before the first LDS minimum.  The minimum over packed keys
+// does not depend on the order of the offers; tag = j (base LEFT: the smallest d wins) or 4095 - j (base RIGHT: the
+// largest).  Rows beyond the base map's, and columns nobody offers to, store 0.
+template <typename VT>
+__global__ __launch_bounds__(kSgmThreads) void ws_pair_wta_kernel(SgmArgs a, const VT *vol, float *out, int out_pitch, int wd, int hd)
+{
+    __shared__ unsigned long long slot[kPairSpan];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nspan = (wd + kPairSpan - 1) / kPairSpan;
+    const int y = blockIdx.x / nspan, c0 = (blockIdx.x % nspan) * kPairSpan;
+    const int cn = min(kPairSpan, wd - c0); // this span's columns
+    for (int i = threadIdx.x; i < kPairSpan; i += kSgmThreads) slot[i] = ~0ull;
+    __syncthreads();
+    if (y < a.h && a.nd > 0) {
+        const int sgn = a.right ? 1 : -1;
+        // base columns that reach [c0, c0 + cn): x = c - sgn d for d in [d0, d0 + nd)
+        const int xa = max(0, a.right ? c0 - a.d0 - a.nd + 1 : c0 + a.d0);
+        const int xb = min(a.w, a.right ? c0 + cn - a.d0 : c0 + cn + a.d0 + a.nd - 1);
+        const uint32_t *krow = a.kr + (size_t)y * a.w;
+        const VT *vrow = vol + (size_t)y * a.w * a.nd;
+        for (int x0 = xa + wave * kPairUnroll; x0 < xb; x0 += (kSgmThreads / 64) * kPairUnroll) {
+            int jlo[kPairUnroll], jhi[kPairUnroll], more = 0;
+#pragma unroll
+            for (int u = 0; u < kPairUnroll; ++u) {
+                const int x = x0 + u;
+                jlo[u] = jhi[u] = 0;
+                if (x >= xb) continue;
+                const uint32_t kr = krow[x];
+                if (kr == 0 || kr == kNoCandidate) continue;
+                // c = x + sgn (d0 + j) in [c0, c0 + cn)
+                const int ja = a.right ? c0 - x - a.d0 : x - a.d0 - c0 - cn + 1, jb = a.right ? c0 + cn - x - a.d0 : x - a.d0 - c0 + 1;
+                jlo[u] = max((int)(kr & 0xffff), ja);
+                jhi[u] = min((int)(kr >> 16), jb);
+                more = max(more, jhi[u] - jlo[u]);
+            }
+            for (int k = 0; k < more; k += 64) {
+                unsigned long long key[kPairUnroll];
+#pragma unroll
+                for (int u = 0; u < kPairUnroll; ++u) {
+                    const int j = jlo[u] + k + lane;
+                    key[u] = ~0ull;
+                    if (j < jhi[u]) key[u] = (unsigned long long)vrow[(size_t)(x0 + u) * a.nd + j] << 12 | (unsigned)(a.right ? 4095 - j : j);
+                }
+#pragma unroll
+                for (int u = 0; u < kPairUnroll; ++u) {
+                    const int j = jlo[u] + k + lane;
+                    const int c = x0 + u + sgn * (a.d0 + j) - c0;
+                    if (j < jhi[u] && c >= 0 && c < cn) atomicMin(&slot[c], key[u]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < cn; i += kSgmThreads) {
+        const unsigned long long key = slot[i];
+        float v = 0.0f;
+        if (key != ~0ull) {
+            const int tag = (int)(key & 4095);
+            v = (float)(a.d0 + (a.right ? 4095 - tag : tag)); // (d == 0, base RIGHT with minD 0: 0.0f, "no disparity")
+        }
+        out[(size_t)y * out_pitch + c0 + i] = v;
+    }
+}
+
 template <int NJ, typename CT, typename ST>
 hipError_t launch_paths(const SgmArgs &a, int paths, hipStream_t s)
 {
@@ -443,8 +516,13 @@ hipError_t launch_sgm(const SgmArgs &a, int paths, hipStream_t s)
     if (const hipError_t e = launch_volumes(a, paths, s); e != hipSuccess) return e;
     const long long n = (long long)a.w * a.h;
     const int wgrid = (int)std::min<long long>((n + 3) / 4, 1 << 20);
-    if (a.sum64) ws_sgm_wta_kernel<unsigned long long><<<wgrid, kSgmThreads, 0, s>>>(a);
-    else ws_sgm_wta_kernel<uint32_t><<<wgrid, kSgmThreads, 0, s>>>(a);
+    if (paths > 0) {
+        if (a.sum64) ws_sgm_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const unsigned long long *>(a.sum));
+        else ws_sgm_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint32_t *>(a.sum));
+    } else {
+        if (a.cost16) ws_sgm_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint16_t *>(a.cost));
+        else ws_sgm_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint32_t *>(a.cost));
+    }
     return hipGetLastError();
 }
 
@@ -460,6 +538,20 @@ hipError_t launch_unique(const SgmArgs &a, const UniqueArgs &u, int paths, hipSt
     } else {
         if (a.cost16) ws_unique_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint16_t *>(a.cost), u);
         else ws_unique_wta_kernel<<<wgrid, kSgmThreads, 0, s>>>(a, static_cast<const uint32_t *>(a.cost), u);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_pair_wta(const SgmArgs &a, int paths, float *out, int out_pitch, int wd, int hd, hipStream_t s)
+{
+    const long long blocks = (long long)hd * ((wd + kPairSpan - 1) / kPairSpan);
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (paths > 0) {
+        if (a.sum64) ws_pair_wta_kernel<<<(int)blocks, kSgmThreads, 0, s>>>(a, static_cast<const unsigned long long *>(a.sum), out, out_pitch, wd, hd);
+        else ws_pair_wta_kernel<<<(int)blocks, kSgmThreads, 0, s>>>(a, static_cast<const uint32_t *>(a.sum), out, out_pitch, wd, hd);
+    } else {
+        if (a.cost16) ws_pair_wta_kernel<<<(int)blocks, kSgmThreads, 0, s>>>(a, static_cast<const uint16_t *>(a.cost), out, out_pitch, wd, hd);
+        else ws_pair_wta_kernel<<<(int)blocks, kSgmThreads, 0, s>>>(a, static_cast<const uint32_t *>(a.cost), out, out_pitch, wd, hd);
     }
     return hipGetLastError();
 }

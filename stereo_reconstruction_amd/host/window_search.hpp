@@ -186,6 +186,31 @@ public:
         return unique(WS_VIEW_RIGHT, uniquenessRatio, confidence, paths, P1, P2);
     }
 
+    // Extension: semi-global matching of one view (baseLeft: the left one), the other view's map derived from the same
+    // sums, and the left-right check of the two in one call (rules in ws_stereo.h, "both views from one volume").
+    // {left map, right map}, as computeDisparityMapsChecked returns them.  uniquenessRatio < 0: no ratio test, else
+    // the test of computeDisparityMap*Unique on the base view's winner.
+    std::pair<MatF64, MatF64> computeDisparityMapsCheckedSGM(int P1, int P2, int paths = 8, float maxDiff = 1.0f, bool fill = false,
+                                                             int uniquenessRatio = -1, bool baseLeft = true)
+    {
+        const ws_params p = params(baseLeft ? WS_VIEW_LEFT : WS_VIEW_RIGHT, 1.0);
+        ws_sgm_params sp;
+        sp.paths = paths;
+        sp.p1 = P1;
+        sp.p2 = P2;
+        ws_unique_params uq;
+        uq.ratio = uniquenessRatio;
+        ws_lr_params lr;
+        lr.max_diff = maxDiff;
+        lr.fill = fill ? WS_LR_FILL_BACKGROUND : WS_LR_FILL_NONE;
+        std::pair<MatF64, MatF64> out(MatF64(leftImage_.rows, leftImage_.cols), MatF64(rightImage_.rows, rightImage_.cols));
+        const ws_image li = detail::to_c(leftImage_), ri = detail::to_c(rightImage_);
+        const int rc = ws_search_pair_host(device_.get(), &p, &sp, uniquenessRatio < 0 ? nullptr : &uq, &lr, &li, &ri, out.first.ptr(),
+                                           out.first.cols, out.second.ptr(), out.second.cols, WS_OUT_F64);
+        if (rc != WS_OK) throw Error(rc, ws_last_error(device_.get()));
+        return out;
+    }
+
 private:
     MatF64 unique(int view, int ratio, std::vector<float> *confidence, int paths, int P1, int P2)
     {
