@@ -33,7 +33,29 @@
 // (wv = 0) take one block of the operand pass each and waves 0 and 1 the copies, the waves with 4 tiles (wv = 1) take
 // two blocks each, the merge of the two waves' candidates and the store of the output row.  A wave's role is a template
 // argument of its march, the rows' ring offsets and byte phases are scalars advanced with a compare and a wrap, and the
-// steady phase of a strip has no guard: its LDS reads are issued together, ahead of the first wait on any of them.
+// steady phase of a strip has no guard.
+//
+// The steady step (PHASE 2, and the tile loop of PHASE 3) of the march with every tile active is a software pipeline,
+// pinned with __builtin_amdgcn_sched_barrier / sched_group_barrier because source order alone does not survive the
+// scheduler (tools/mfma_listing.py prints what came out; profiles/mfma_pipeline/README.md holds the tables):
+//   1. what the step reads and the step before it does not write -- the two raw A rows, the NTL operand quads of the
+//      leaving row, the operand pass's rows -- is read a tile's keys ahead of the barrier of the step BEFORE
+//      (ahead_load; the cursors advance in the middle of a step, behind their last use), so it has landed when the
+//      barrier opens.  Behind the barrier only the NTL operand quads of the entering row and the bias quads of tile 0
+//      are read, together, ahead of the first wait.  LDS returns in issue order, so each wait is a counted lgkmcnt(N)
+//      that covers what the next instruction consumes and nothing younger;
+//   2. the entering MFMAs of all tiles, then the leaving MFMAs, in four groups (entering 0 .. NTL - 3 | NTL - 2,
+//      NTL - 1 | leaving 0, 1 | then one leaving MFMA per key block): inside a group the compiler may take any order,
+//      and no order puts two MFMAs on one accumulator side by side.  The operand pass's VALU (two halves per block:
+//      items_enter, items_leave) sits between the MFMAs of the first three groups;
+//   3. tile t's keys and minimum run under the leaving MFMA of tile t + 2; the bias quads of tile t + 1 (a double
+//      buffer of 2 x 16 registers) are read a whole key block ahead of their use;
+//   4. the two lane halves of a column meet in two v_permlane32_swap and a compare / select (mfma_pair_best): no LDS
+//      round trip and no branch in front of the barrier.
+// The march that skips tiles (a narrow disparity range) and the phases before the first leaving row keep the simple
+// tile loop.  The flush is where it was: the merge pair it reads is written by the partner wave in the step before, so
+// it is read behind the barrier, first of all reads; flush_store follows the half merge.  What each item measured, and
+// what was dropped (a static s_setprio for the 4-tile waves: slower): profiles/mfma_pipeline/README.md.
 #pragma once
 #include "ws_march_kernel.h"
 
@@ -120,6 +142,28 @@ __device__ __forceinline__ uint32_t mfma_pair_sum(uint32_t x)
     const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
     return r[0] + r[1];
 }
+
+// lane n and lane n + 32 both get the better of their two candidates (smaller cost word, then smaller G): two
+// v_permlane32_swap, no LDS, no branch
+__device__ __forceinline__ void mfma_pair_best(int &cw, int &G)
+{
+    const auto c = __builtin_amdgcn_permlane32_swap((uint32_t)cw, (uint32_t)cw, false, false); // {lane n's, lane n + 32's} in both lanes
+    const auto q = __builtin_amdgcn_permlane32_swap((uint32_t)G, (uint32_t)G, false, false);
+    const int c0 = (int)c[0], c1 = (int)c[1], g0 = (int)q[0], g1 = (int)q[1];
+    const bool up = c1 < c0 || (c1 == c0 && g1 < g0);
+    cw = up ? c1 : c0;
+    G = up ? g1 : g0;
+}
+
+// The sizes of the VALU groups that sched_group_barrier places behind the MFMAs of the steady step.  They are read off
+// the gfx950 listing, not derived: kPipeValuA = the instructions that make the entering row's A operand in front of
+// the first MFMA (4 v_alignbyte + 4 v_bitop3); kPipeValu[role] = the VALU of the operand pass that lies between the
+// first six MFMAs (about 45 instructions per block: one block on a 5-tile wave, two on a 4-tile wave) divided by the
+// MFMAs it is spread under, rounded up.  A group asks for "up to" its size, so a number that is off, or another
+// compiler's instruction count, regroups the VALU and changes no result; after a toolchain change
+// tools/mfma_listing.py is the check (no neighbouring MFMAs on one accumulator, the read-to-wait distances).
+constexpr int kPipeValuA = 8;
+constexpr int kPipeValu[2] = {8, 14};
 
 // a ring cursor: on by one row, back to the ring's first row behind its last
 __device__ __forceinline__ void mfma_advance(uint32_t &at, uint32_t row, uint32_t end)
@@ -296,32 +340,55 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                 if constexpr (decltype(leaves)::value) il[k] = lds_load128(it_lane + 1024u * (uint32_t)k + oSq);
             }
         };
-        // row iu enters the windows of the target centres, row iu - WH leaves them
+        // what a pipelined step reads before the barrier of the step before it (issue order = order of use): the two
+        // raw A rows, the leaving row's operands, the operand pass's rows.  None of it is written in that step: the A
+        // rows were copied two and more steps earlier, the raw B row one step earlier, the leaving rows' operands WH - 1
+        // and WH steps earlier.  (The entering row's operands, the bias' values and the merge pairs ARE written in it.)
+        MfmaRaw n_rae{}, n_ral{};
+        uint4 n_bl[NTL];
+        auto ahead_load = [&]() __attribute__((always_inline)) {
+            n_rae = mfma_raw_load(pA_lane + aIn + phIn);
+            n_ral = mfma_raw_load(pA_lane + aOut + phOut);
+#pragma unroll
+            for (int t = 0; t < NTL; ++t) n_bl[t] = lds_load128(opB_lane + oOut + 1024u * (uint32_t)t);
+            items_load(std::true_type());
+        };
+        // row iu enters the windows of the target centres, row iu - WH leaves them; block k in two parts, so that the
+        // pipelined step can place them under different MFMAs: the entering row's operands and sums ...
+        uint32_t iu_[NI];
+        auto items_enter = [&](int k) __attribute__((always_inline)) {
+            ws_i32x4 c = mfma_raw_align(ir[k]);
+            c ^= (int)0x80808080u;
+            lds_store128(it_lane + 1024u * (uint32_t)k + oWr, make_uint4((uint32_t)c.x, (uint32_t)c.y, (uint32_t)c.z, (uint32_t)c.w));
+            const ws_i32x4 cm = c & amask; // (the bytes past the window count as zeros)
+            int q = 0, t = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                q = __builtin_amdgcn_sdot4(c[j], cm[j], q, false);
+                t = __builtin_amdgcn_sdot4(cm[j], 0x01010101, t, false);
+            }
+            iu_[k] = (uint32_t)q + 2u * (uint32_t)t;
+        };
+        // ... and the leaving row's sum, the lane pair's total and the bias' value
+        auto items_leave = [&](int iu, int k, auto leaves) __attribute__((always_inline)) {
+            uint32_t u = iu_[k];
+            if constexpr (decltype(leaves)::value) {
+                const ws_i32x4 l = {(int)il[k].x, (int)il[k].y, (int)il[k].z, (int)il[k].w};
+                const ws_i32x4 lm = l & amask;
+                int lq = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) lq = __builtin_amdgcn_sdot4(l[j], lm[j], lq, false);
+                u -= (uint32_t)lq;
+            }
+            gsum[k] += mfma_pair_sum(u);
+            // (both lanes of a pair write the one word)
+            *reinterpret_cast<lds_u32 *>((uintptr_t)(bi_lane + 4u * (uint32_t)((iu & 1) * L.nvc + 32 * k))) = (gsum[k] << KT) + btag[k];
+        };
         auto items_finish = [&](int iu, auto leaves) __attribute__((always_inline)) {
 #pragma unroll
             for (int k = 0; k < NI; ++k) {
-                ws_i32x4 c = mfma_raw_align(ir[k]);
-                c ^= (int)0x80808080u;
-                lds_store128(it_lane + 1024u * (uint32_t)k + oWr, make_uint4((uint32_t)c.x, (uint32_t)c.y, (uint32_t)c.z, (uint32_t)c.w));
-                const ws_i32x4 cm = c & amask; // (the bytes past the window count as zeros)
-                int q = 0, t = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    q = __builtin_amdgcn_sdot4(c[j], cm[j], q, false);
-                    t = __builtin_amdgcn_sdot4(cm[j], 0x01010101, t, false);
-                }
-                uint32_t u = (uint32_t)q + 2u * (uint32_t)t;
-                if constexpr (decltype(leaves)::value) {
-                    const ws_i32x4 l = {(int)il[k].x, (int)il[k].y, (int)il[k].z, (int)il[k].w};
-                    const ws_i32x4 lm = l & amask;
-                    int lq = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) lq = __builtin_amdgcn_sdot4(l[j], lm[j], lq, false);
-                    u -= (uint32_t)lq;
-                }
-                gsum[k] += mfma_pair_sum(u);
-                // (both lanes of a pair write the one word)
-                *reinterpret_cast<lds_u32 *>((uintptr_t)(bi_lane + 4u * (uint32_t)((iu & 1) * L.nvc + 32 * k))) = (gsum[k] << KT) + btag[k];
+                items_enter(k);
+                items_leave(iu, k, leaves);
             }
         };
 
@@ -359,6 +426,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
             // (the steady phase: every stage has its row), 3: the same with the strip's end in sight
             constexpr int PHASE = decltype(phase)::value;
             constexpr bool STEADY = PHASE == 2;
+            constexpr bool PIPE = ALL && PHASE >= 2; // the pipelined tile loop; the march that skips tiles keeps the simple one
             using Leaves = std::integral_constant<bool, (PHASE >= 1)>; // row s + 1 - WH exists
             Flush fl{};
             if constexpr (WV == 1 && PHASE >= 2) {
@@ -372,21 +440,122 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
             // a block -- up to 8, when the row enters and again when it leaves -- read one aligned ds_read_b128 each, and
             // the bias' values of step s + 1
             const bool stage = STEADY || (s + 1 >= 0 && s + 1 < nsteps);
-            if constexpr (STEADY) items_load(Leaves());
+            if constexpr (STEADY) {
+                if (!(PIPE && wave_on)) items_load(Leaves()); // (a pipelined step's were read ahead: ahead_load)
+            }
             // the matrix cores: row s enters every window, row s - WH leaves it; keys and the output row
             if (PHASE >= 0 && wave_on) {
-                const MfmaRaw rae = mfma_raw_load(pA_lane + aIn + phIn);
-                MfmaRaw ral{};
-                if constexpr (PHASE >= 2) ral = mfma_raw_load(pA_lane + aOut + phOut);
+                MfmaRaw rae{}, ral{};
+                if constexpr (PIPE) {
+                    rae = n_rae, ral = n_ral;
+                } else {
+                    rae = mfma_raw_load(pA_lane + aIn + phIn);
+                    if constexpr (PHASE >= 2) ral = mfma_raw_load(pA_lane + aOut + phOut);
+                }
                 const uint32_t opBe = opB_lane + oIn, opBl = opB_lane + oOut;
-                if constexpr (STEADY) items_finish(s + 1, Leaves());
-                else if (stage) { items_load(Leaves()); items_finish(s + 1, Leaves()); }
+                (void)opBl;
+                if constexpr (!PIPE) {
+                    if constexpr (STEADY) items_finish(s + 1, Leaves());
+                    else if (stage) { items_load(Leaves()); items_finish(s + 1, Leaves()); }
+                }
                 // -a^ - 1 = a xor 0x7f, a^ = a xor 0x80; the pad must stay zero
-                const ws_i32x4 ae = (mfma_raw_align(rae) ^ (int)0x7f7f7f7fu) & amask;
-                ws_i32x4 al{};
-                if constexpr (PHASE >= 2) al = (mfma_raw_align(ral) ^ (int)0x80808080u) & amask;
+                ws_i32x4 ae{}, al{};
+                if constexpr (!PIPE) {
+                    ae = (mfma_raw_align(rae) ^ (int)0x7f7f7f7fu) & amask;
+                    if constexpr (PHASE >= 2) al = (mfma_raw_align(ral) ^ (int)0x80808080u) & amask;
+                }
                 int bestk = INT_MAX, bestt = 0;
                 const uint32_t brow = biasr + 4u * (uint32_t)((s & 1) * L.nvc + 32 * (wx + WV * NVW) + 4 * h);
+                if constexpr (PIPE) {
+                    // ---- the pipelined tile loop (see the header) -----------------------------------------------
+                    // LDS operations return in issue order, so the compiler's waits on this sequence are counts
+                    uint4 be4[NTL], bq[2][4];
+#pragma unroll
+                    for (int t = 0; t < NTL; ++t) be4[t] = lds_load128(opBe + 1024u * (uint32_t)t);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) bq[0][q] = lds_load128(brow + 4u * (uint32_t)(8 * q));
+                    __builtin_amdgcn_sched_barrier(0); // every read above is in flight before the first wait
+                    // Four groups of MFMAs with the operand pass's VALU between them.  Inside a group the compiler
+                    // may take the MFMAs in any order, so the groups are cut where no order puts two MFMAs on one
+                    // accumulator side by side: entering tiles 0 .. NTL - 3 | NTL - 2, NTL - 1 | leaving 0, 1 | 2 .. NTL - 1
+                    auto enter = [&](int t) __attribute__((always_inline)) {
+                        const ws_i32x4 be = {(int)be4[t].x, (int)be4[t].y, (int)be4[t].z, (int)be4[t].w};
+                        acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(be, ae, acc[t], 0, 0, 0);
+                    };
+                    auto leave = [&](int t) __attribute__((always_inline)) {
+                        const ws_i32x4 bl = {(int)n_bl[t].x, (int)n_bl[t].y, (int)n_bl[t].z, (int)n_bl[t].w};
+                        acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bl, al, acc[t], 0, 0, 0);
+                    };
+                    constexpr int VG = kPipeValu[WV];
+                    ae = (mfma_raw_align(rae) ^ (int)0x7f7f7f7fu) & amask;
+                    al = (mfma_raw_align(ral) ^ (int)0x80808080u) & amask;
+#pragma unroll
+                    for (int t = 0; t < NTL - 2; ++t) enter(t);
+                    if constexpr (STEADY) items_enter(0);
+                    __builtin_amdgcn_sched_group_barrier(0x2, kPipeValuA, 0); // (the entering row's A operand)
+#pragma unroll
+                    for (int t = 0; t < NTL - 2; ++t) {
+                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    enter(NTL - 2), enter(NTL - 1);
+                    if constexpr (STEADY) {
+                        if constexpr (NI == 2) items_enter(1);
+                        else items_leave(s + 1, 0, Leaves());
+                    }
+                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (!STEADY) {
+                        if (stage) { items_load(Leaves()); items_finish(s + 1, Leaves()); }
+                    }
+                    leave(0), leave(1);
+                    if constexpr (STEADY && NI == 2) items_leave(s + 1, 0, Leaves());
+                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (STEADY && NI == 2) {
+                        items_leave(s + 1, 1, Leaves());
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    advance(); // (nothing below names a cursor of this step)
+#pragma unroll
+                    for (int t = 0; t < NTL; ++t) {
+                        // the next step's reads, two tiles' keys ahead of the barrier; the next tile's bias quads (they
+                        // have a tile's keys to land in) and the leaving MFMA of the tile after it, then this tile's keys
+                        // under that MFMA
+                        if (t == NTL - 2) ahead_load();
+                        if (t + 1 < NTL) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) bq[(t + 1) & 1][q] = lds_load128(brow + 4u * (uint32_t)(32 * (t + 1) + 8 * q));
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (t + 2 < NTL) {
+                            leave(t + 2);
+                            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                        }
+                        int key[16];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const uint4 b4 = bq[t & 1][q];
+                            key[4 * q + 0] = (int)(((uint32_t)acc[t][4 * q + 0] << (KT + 1)) + b4.x);
+                            key[4 * q + 1] = (int)(((uint32_t)acc[t][4 * q + 1] << (KT + 1)) + b4.y);
+                            key[4 * q + 2] = (int)(((uint32_t)acc[t][4 * q + 2] << (KT + 1)) + b4.z);
+                            key[4 * q + 3] = (int)(((uint32_t)acc[t][4 * q + 3] << (KT + 1)) + b4.w);
+                        }
+                        int km = min(key[0], key[1]);
+#pragma unroll
+                        for (int i = 2; i < 16; i += 2) km = min(km, min(key[i], key[i + 1])); // v_min3_i32
+                        const bool better = (km | ((1 << KT) - 1)) < bestk;
+                        bestk = better ? km : bestk;
+                        bestt = better ? t : bestt;
+                    }
+                } else
 #pragma unroll
                 for (int t = 0; t < NTL; ++t) { // (t: the tile's index in this wave)
                     if constexpr (!ALL) {
@@ -424,8 +593,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                     const int i_best = bestk & ((1 << KT) - 1);
                     int G = 32 * (bestt + WV * NVW) + (i_best & 3) + 8 * (i_best >> 2) + 4 * h;
                     int cw = bestk >> KT; // the cost word
-                    const int cw_o = __shfl_xor(cw, 32, 64), G_o = __shfl_xor(G, 32, 64);
-                    if (cw_o < cw || (cw_o == cw && G_o < G)) { cw = cw_o; G = G_o; }
+                    mfma_pair_best(cw, G);
                     if constexpr (WV == 1 && PHASE >= 2) flush_store(s - 1, fl);
                     // the first wave of a column leaves its best in LDS for the second, which writes the row out in the
                     // next step (both lanes of a column write the one pair)
@@ -444,7 +612,15 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                 if (wave < 2) dma_wait(); // (the copy lands inside its step: a wait that lets it span the barrier measured slower)
             }
             __syncthreads();
-            advance();
+            if constexpr (PIPE) {
+                if (!wave_on) advance(); // (a wave with columns advanced in the middle of its step)
+            } else {
+                advance();
+                // the first pipelined step's reads
+                if constexpr (ALL && PHASE == 1) {
+                    if (wave_on) ahead_load();
+                }
+            }
         };
 
         int s = -3;
