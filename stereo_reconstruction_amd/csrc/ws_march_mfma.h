@@ -49,7 +49,8 @@
 //      and no order puts two MFMAs on one accumulator side by side.  The operand pass's VALU (two halves per block:
 //      items_enter, items_leave) sits between the MFMAs of the first three groups;
 //   3. tile t's keys and minimum run under the leaving MFMA of tile t + 2; the bias quads of tile t + 1 (a double
-//      buffer of 2 x 16 registers) are read a whole key block ahead of their use;
+//      buffer of 2 x 16 registers) are read a whole key block ahead of their use.  The minimum of the 16 keys is one
+//      chain, min(min(km, a), b): one v_min and 7 v_min3 (a tree of pairs compiles to 7 v_min + 4 v_min3);
 //   4. the two lane halves of a column meet in two v_permlane32_swap and a compare / select (mfma_pair_best): no LDS
 //      round trip and no branch in front of the barrier.
 // The march that skips tiles (a narrow disparity range) and the phases before the first leaving row keep the simple
@@ -550,7 +551,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                         }
                         int km = min(key[0], key[1]);
 #pragma unroll
-                        for (int i = 2; i < 16; i += 2) km = min(km, min(key[i], key[i + 1])); // v_min3_i32
+                        for (int i = 2; i < 16; i += 2) km = min(min(km, key[i]), key[i + 1]); // one v_min, then 7 v_min3_i32
                         const bool better = (km | ((1 << KT) - 1)) < bestk;
                         bestk = better ? km : bestk;
                         bestt = better ? t : bestt;
@@ -581,7 +582,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                         }
                         int km = min(key[0], key[1]);
 #pragma unroll
-                        for (int i = 2; i < 16; i += 2) km = min(km, min(key[i], key[i + 1])); // v_min3_i32
+                        for (int i = 2; i < 16; i += 2) km = min(min(km, key[i]), key[i + 1]); // one v_min, then 7 v_min3_i32
                         // a later tile (smaller d) wins on a strictly smaller cost only
                         const bool better = (km | ((1 << KT) - 1)) < bestk;
                         bestk = better ? km : bestk;
