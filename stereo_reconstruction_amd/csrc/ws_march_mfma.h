@@ -28,7 +28,8 @@
 // image, and stay raw: every consumer centres the bytes in an instruction it issues anyway.  One barrier per step:
 //   step s:  copy row s + 3  |  (row s + 2 rests: the copies' look-ahead)  |  row s + 1 of the target image: one pass
 //            makes its lane-linear MFMA operands (a ring of WH + 2 rows of 12 KB) and, from the same registers, the
-//            bias' values  |  MFMAs, keys of row s, output of row s - 1.
+//            bias' values (the row's sum of squares stays in the pad of its operand entry and is read back, not computed
+//            again, when the row leaves the windows)  |  MFMAs, keys of row s, output of row s - 1.
 // The step ends when its slowest wave reaches the barrier, so the roles are dealt by tile share: the waves with 5 tiles
 // (wv = 0) take one block of the operand pass each and waves 0 and 1 the copies, the waves with 4 tiles (wv = 1) take
 // two blocks each, the merge of the two waves' candidates and the store of the output row.  A wave's role is a template
@@ -159,12 +160,12 @@ __device__ __forceinline__ void mfma_pair_best(int &cw, int &G)
 // The sizes of the VALU groups that sched_group_barrier places behind the MFMAs of the steady step.  They are read off
 // the gfx950 listing, not derived: kPipeValuA = the instructions that make the entering row's A operand in front of
 // the first MFMA (4 v_alignbyte + 4 v_bitop3); kPipeValu[role] = the VALU of the operand pass that lies between the
-// first six MFMAs (about 45 instructions per block: one block on a 5-tile wave, two on a 4-tile wave) divided by the
+// first six MFMAs (about 37 instructions per block: one block on a 5-tile wave, two on a 4-tile wave) divided by the
 // MFMAs it is spread under, rounded up.  A group asks for "up to" its size, so a number that is off, or another
 // compiler's instruction count, regroups the VALU and changes no result; after a toolchain change
 // tools/mfma_listing.py is the check (no neighbouring MFMAs on one accumulator, the read-to-wait distances).
 constexpr int kPipeValuA = 8;
-constexpr int kPipeValu[2] = {8, 14};
+constexpr int kPipeValu[2] = {7, 12};
 
 // a ring cursor: on by one row, back to the ring's first row behind its last
 __device__ __forceinline__ void mfma_advance(uint32_t &at, uint32_t row, uint32_t end)
@@ -316,6 +317,11 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
         const uint32_t st_lane = ringB + 3u * (uint32_t)(32 * blk0 + n) + 16u * (uint32_t)h; // this lane's 16 bytes in a raw B row
         const uint32_t it_lane = opB + 1024u * (uint32_t)blk0 + 16u * (uint32_t)lane;         // ... in an operand row
         const uint32_t bi_lane = biasr + 4u * (uint32_t)(32 * blk0 + n);
+        // An operand entry has room for the row's sum of squares: in the h = 1 lane of a pair dwords 2 and 3 are bytes
+        // 24 .. 31 of the centre's 32, which amask zeroes on the A side, so what the B side holds there is multiplied by
+        // zero.  Lane h of the pair keeps its half sum in dword 2 + h of that entry and reads it back when the row leaves.
+        static_assert(K <= 24, "bytes 24 .. 31 of an operand entry are pad");
+        const uint32_t sq_lane = opB + 1024u * (uint32_t)blk0 + 16u * (uint32_t)(32 + n) + 8u + 4u * (uint32_t)h;
 
         // ---- the accumulators -----------------------------------------------------------------------------------
         // tile t, register i: e = d - d_lo = 32 (NV - 1 - t) + n - m; outside [0, dspan]: poisoned for good
@@ -333,12 +339,12 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
         }
 
         MfmaRaw ir[NI]; // the entering row's raw bytes
-        uint4 il[NI];   // the leaving row's operand bytes
+        uint32_t il[NI]; // the leaving row's half sum of squares, as it was stored when the row entered
         auto items_load = [&](auto leaves) __attribute__((always_inline)) {
 #pragma unroll
             for (int k = 0; k < NI; ++k) {
                 ir[k] = mfma_raw_load(st_lane + 96u * (uint32_t)k + bSt + phSt);
-                if constexpr (decltype(leaves)::value) il[k] = lds_load128(it_lane + 1024u * (uint32_t)k + oSq);
+                if constexpr (decltype(leaves)::value) il[k] = *lds_at32(sq_lane + 1024u * (uint32_t)k + oSq);
             }
         };
         // what a pipelined step reads before the barrier of the step before it (issue order = order of use): the two
@@ -368,19 +374,13 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                 q = __builtin_amdgcn_sdot4(c[j], cm[j], q, false);
                 t = __builtin_amdgcn_sdot4(cm[j], 0x01010101, t, false);
             }
+            *reinterpret_cast<lds_u32 *>((uintptr_t)(sq_lane + 1024u * (uint32_t)k + oWr)) = (uint32_t)q; // (behind the entry's own store)
             iu_[k] = (uint32_t)q + 2u * (uint32_t)t;
         };
-        // ... and the leaving row's sum, the lane pair's total and the bias' value
+        // ... and the leaving row's sum (read back, not computed again), the lane pair's total and the bias' value
         auto items_leave = [&](int iu, int k, auto leaves) __attribute__((always_inline)) {
             uint32_t u = iu_[k];
-            if constexpr (decltype(leaves)::value) {
-                const ws_i32x4 l = {(int)il[k].x, (int)il[k].y, (int)il[k].z, (int)il[k].w};
-                const ws_i32x4 lm = l & amask;
-                int lq = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) lq = __builtin_amdgcn_sdot4(l[j], lm[j], lq, false);
-                u -= (uint32_t)lq;
-            }
+            if constexpr (decltype(leaves)::value) u -= il[k];
             gsum[k] += mfma_pair_sum(u);
             // (both lanes of a pair write the one word)
             *reinterpret_cast<lds_u32 *>((uintptr_t)(bi_lane + 4u * (uint32_t)((iu & 1) * L.nvc + 32 * k))) = (gsum[k] << KT) + btag[k];
