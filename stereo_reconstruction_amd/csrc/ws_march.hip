@@ -84,6 +84,7 @@ const MarchKnobs &march_knobs()
         k.flush_wave = num("WS_FLUSH_WAVE", -1);
         k.stage_agap = num("WS_STAGE_AGAP", 0);
         k.mfma = num("WS_MARCH_MFMA", -1);
+        k.mfma_strip_rows = num("WS_MFMA_STRIP_ROWS", 0);
         k.stencil_forced = getenv("WS_PLAN_SLOTS") || getenv("WS_PLAN_THREADS") || getenv("WS_MAX_CHUNKS") || getenv("WS_MARCH_ND");
         return k;
     }();

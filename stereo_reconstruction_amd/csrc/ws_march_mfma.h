@@ -15,10 +15,13 @@
 //     complemented (~a^ = -a^ - 1), the leaving row plain:  Acc += -R(e) - T(e, v) + R(l),  T(y, v) = sum_k b^[y][k].
 //     After any number of steps Acc = -(cross sum over the window's rows) - E(v), E(v) = sum of T over every row entered.
 //   * key = (Acc << (KT + 1)) + bias'[v],  bias'[v] = ((window sum of b^^2) + 2 E(v)) << KT | tie tag, poisoned where the
-//     target centre is invalid; all modulo 2^32, the key exact.  Candidates outside [d_lo, d_hi] are poisoned through the
-//     accumulator's initial value (kPoison >> (KT + 1)), which costs nothing per step.
-//   * v_min3 over a tile's 16 registers (4-bit tags: register order is disparity order), a strict '<' between tiles taken
-//     in the preferred order of d, and one exchange between lane n and lane n + 32.
+//     target centre is invalid.  KT = 3, so the shift is 4 and the keys of an aligned register pair are ONE
+//     v_lshl_add_u64 on the pair and its two bias words; accumulators and bias words carry uniform offsets that keep
+//     every word non-negative and every sum inside its word (kMfmaA0 .. below), the key exact and compared unsigned.
+//     Candidates outside [d_lo, d_hi] are poisoned through the accumulator's initial value, which costs nothing per step.
+//   * per tile two chains of v_min3_u32, over the low and the high words of the 8 pairs (3-bit tags: the pair's index,
+//     register order is disparity order), a compare between the chains, a strict '<' between tiles taken in the
+//     preferred order of d, and one exchange between lane n and lane n + 32.
 //
 // Geometry: a workgroup of 8 waves owns a tile of 128 columns and a strip of rows; two waves share columns 32 wx .. 32 wx + 31
 // and split their NV tiles of 32 target centres (NV = 9 covers 256 disparities) 5 : 4, each with its 16 accumulators per
@@ -50,8 +53,8 @@
 //      and no order puts two MFMAs on one accumulator side by side.  The operand pass's VALU (two halves per block:
 //      items_enter, items_leave) sits between the MFMAs of the first three groups;
 //   3. tile t's keys and minimum run under the leaving MFMA of tile t + 2; the bias quads of tile t + 1 (a double
-//      buffer of 2 x 16 registers) are read a whole key block ahead of their use.  The minimum of the 16 keys is one
-//      chain, min(min(km, a), b): one v_min and 7 v_min3 (a tree of pairs compiles to 7 v_min + 4 v_min3);
+//      buffer of 2 x 16 registers) are read a whole key block ahead of their use.  The minimum of the 16 keys is two
+//      chains of 8, min(min(km, a), b): one v_min and 3 v_min3 each (mfma_tile_best);
 //   4. the two lane halves of a column meet in two v_permlane32_swap and a compare / select (mfma_pair_best): no LDS
 //      round trip and no branch in front of the barrier.
 // The march that skips tiles (a narrow disparity range) and the phases before the first leaving row keep the simple
@@ -67,13 +70,48 @@ typedef int ws_i32x4 __attribute__((ext_vector_type(4)));
 typedef int ws_i32x16 __attribute__((ext_vector_type(16)));
 typedef int ws_i32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) ws_i32x2 lds_i64;
+typedef unsigned long long ws_u64x8 __attribute__((ext_vector_type(8)));
+typedef unsigned long long ws_u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMfmaXWaves = 4; // waves side by side: 128 columns per tile
 constexpr int kMfmaVWaves = 2; // waves that share 32 columns and split their candidates
 constexpr int kMfmaWaves = kMfmaXWaves * kMfmaVWaves;
 constexpr int kMfmaVTiles = 9; // tiles of 32 target centres per 32 columns: 32 + 255 candidate columns -> up to 256 disparities
 constexpr int kMfmaTilesPerWave = (kMfmaVTiles + kMfmaVWaves - 1) / kMfmaVWaves;
-constexpr int kMfmaKT = 4;     // tie-tag bits: the 16 registers of a tile
+constexpr int kMfmaKT = 3;     // tie-tag bits: the 8 register pairs of a tile
+
+// ---- the key's ranges ------------------------------------------------------------------------------------------------
+// Two keys come out of one v_lshl_add_u64 on an aligned register pair, (Acc << 4) + bias' on 64 bits, so nothing may
+// cross from the low word into the high one: the 4 bits shifted out of the low accumulator are zeros and the low sum
+// does not carry.  Accumulators and bias words are therefore kept non-negative by uniform offsets, and every bound
+// follows from the longest strip the kernel is taken for, kMfmaMaxSteps rows entered (the launcher's rule refuses
+// longer ones).  For a window of K bytes per row and WH rows, centred bytes in [-128, 127]:
+//   |cross sum| <= XB = 128^2 K WH,   |E(v)| <= EB = 128 K kMfmaMaxSteps,   0 <= window sum of b^^2 <= XB,
+//   Acc = -(cross sum) - E in [-(XB + EB), XB + EB],   gsum = (sum of b^^2) + 2 E in [-2 EB, XB + 2 EB],
+//   cost word 2 Acc + gsum = (sum of b^^2) - 2 (cross sum) in [-2 XB, 3 XB]   (E cancels).
+// Acc starts at kMfmaA0 (+ kMfmaAccPoison outside [d_lo, d_hi]), gsum at kMfmaG0 (+ kMfmaBiasPoison at an invalid
+// centre); the cost word carries kMfmaC0 = 2 A0 + G0, the same for every candidate, so their order is what it was.
+constexpr int kMfmaMaxSteps = 8192;
+constexpr long long kMfmaA0 = 1LL << 25, kMfmaAccPoison = 1LL << 27;
+constexpr long long kMfmaG0 = 1LL << 26, kMfmaBiasPoison = 1LL << 26;
+constexpr long long kMfmaC0 = 2 * kMfmaA0 + kMfmaG0;
+constexpr long long kMfmaValidBound = kMfmaC0 + (1LL << 25); // a cost word at or above it holds a poison
+template <int K, int WH>
+constexpr bool mfma_key_ranges_hold()
+{
+    constexpr long long XB = 128LL * 128 * K * WH, EB = 128LL * K * kMfmaMaxSteps;
+    static_assert(XB + EB < kMfmaA0, "Acc + A0 stays positive");
+    static_assert(kMfmaA0 + XB + EB + kMfmaAccPoison < (1LL << 28), "the 4 bits shifted out of an accumulator are zeros");
+    static_assert(2 * EB <= kMfmaG0, "gsum + G0 stays non-negative");
+    static_assert(((kMfmaG0 + XB + 2 * EB + kMfmaBiasPoison) << kMfmaKT) + (1 << kMfmaKT) <= (1LL << 31), "a bias word is a positive int");
+    static_assert(kMfmaC0 - 2 * XB >= 0, "a cost word is positive");
+    static_assert(((kMfmaC0 + 3 * XB + 2 * kMfmaAccPoison + kMfmaBiasPoison) << kMfmaKT) + (1 << kMfmaKT) <= (1LL << 32),
+                  "a doubly poisoned key does not wrap, and the low word of a pair does not carry");
+    static_assert(kMfmaC0 + 3 * XB < kMfmaValidBound, "every valid cost word is below the bound");
+    static_assert(kMfmaC0 - 2 * XB + 2 * kMfmaAccPoison >= kMfmaValidBound && kMfmaC0 - 2 * XB + kMfmaBiasPoison >= kMfmaValidBound,
+                  "every poisoned cost word is at or above it");
+    return true;
+}
 
 struct MfmaLds {
     int n_a, n_b;   // pixels per raw row the copies fetch
@@ -164,8 +202,52 @@ __device__ __forceinline__ void mfma_pair_best(int &cw, int &G)
 // MFMAs it is spread under, rounded up.  A group asks for "up to" its size, so a number that is off, or another
 // compiler's instruction count, regroups the VALU and changes no result; after a toolchain change
 // tools/mfma_listing.py is the check (no neighbouring MFMAs on one accumulator, the read-to-wait distances).
+// (Read again off the listing with the packed keys: the operand pass is what it was, 37 instructions per block with
+// the bias' word still one v_lshl_add_u32, and so are the sizes; the shorter key blocks lie behind these groups.)
 constexpr int kPipeValuA = 8;
 constexpr int kPipeValu[2] = {7, 12};
+
+// The keys of a tile and their minimum.  Registers 2 q, 2 q + 1 and their two bias words are aligned 64-bit pairs, and
+// (Acc << 4) + bias' on the pair is both keys (kMfmaKT above: nothing crosses between the words): 8 v_lshl_add_u64.  The
+// tag of a key is its pair's index q, so the minimum runs in two chains, L over the low words (registers 0, 2, .. 14)
+// and H over the high words (1, 3, .. 15), one v_min and three v_min3_u32 each.  Inside a chain the tags order equal
+// costs; between them H wins exactly when kmH < kmL as integers: on equal cost register 2 qH + 1 is preferred over
+// 2 qL exactly when qH < qL.  Between tiles a later tile (smaller d) wins on a strictly smaller cost only.
+// The tile-level chain keeps the best key, its tile and the L minimum of that tile: the key is min(kmL, kmH), so H won
+// exactly where it differs from the L minimum, which is asked once behind the last tile (mfma_best_code: 2 t + isH)
+// and costs one select per tile.  FIRST: no tile before this one (the best so far is "none").
+struct MfmaBest {
+    uint32_t k, l, t;
+};
+__device__ __forceinline__ uint32_t mfma_best_code(const MfmaBest &b) { return 2u * b.t + (b.k < b.l ? 1u : 0u); }
+template <bool FIRST>
+__device__ __forceinline__ void mfma_tile_best(const ws_i32x16 &acc, const uint4 (&b4)[4], int t, MfmaBest &best)
+{
+    const ws_u64x8 a = __builtin_bit_cast(ws_u64x8, acc);
+    uint32_t lo[8], hi[8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const ws_u64x2 b = __builtin_bit_cast(ws_u64x2, b4[q]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            // (plain C++, not inline assembly: the compiler must see a VALU read of an MFMA result to keep its distance)
+            const unsigned long long k = (a[2 * q + j] << (kMfmaKT + 1)) + b[j];
+            lo[2 * q + j] = (uint32_t)k, hi[2 * q + j] = (uint32_t)(k >> 32);
+        }
+    }
+    uint32_t kl = min(lo[0], lo[1]), kh = min(hi[0], hi[1]);
+#pragma unroll
+    for (int q = 2; q < 8; q += 2) kl = min(min(kl, lo[q]), lo[q + 1]), kh = min(min(kh, hi[q]), hi[q + 1]);
+    const uint32_t km = min(kl, kh);
+    if constexpr (FIRST) {
+        best = MfmaBest{km, kl, (uint32_t)t};
+    } else {
+        const bool better = (km | ((1u << kMfmaKT) - 1u)) < best.k;
+        best.k = better ? km : best.k;
+        best.l = better ? kl : best.l;
+        best.t = better ? (uint32_t)t : best.t;
+    }
+}
 
 // a ring cursor: on by one row, back to the ring's first row behind its last
 __device__ __forceinline__ void mfma_advance(uint32_t &at, uint32_t row, uint32_t end)
@@ -181,9 +263,8 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
     constexpr int NR = mfma_ring_rows(WH);
     constexpr int K = 3 * WW;
     static_assert(K <= 32 && K > 16, "one row of the window is one K = 32 step, its pad in the upper lane half");
-    // a centred cost word sum b^^2 - 2 sum a^.b^ lies in [-128^2, 128^2 + 2 * 127 * 128] per byte of the window
-    static_assert((long long)(128 * 128 + 2 * 127 * 128) * K * WH * (1 << KT) < (long long)kValidKeyBound, "keys stay inside (-2^28, 2^28)");
-    static_assert(kPoison % (1 << (KT + 1)) == 0, "the poison survives the shift");
+    static_assert(mfma_key_ranges_hold<K, WH>(), "the ranges of the packed key (above)");
+    static_assert(KT == 3, "(Acc << (KT + 1)) + bias' is one v_lshl_add_u64 per register pair for a shift of 4");
     static_assert(kMfmaXWaves == 4 && kMfmaVWaves == 2, "wave >> 2 is the share of the tiles");
 
     extern __shared__ uint4 ws_smem4[];
@@ -304,14 +385,16 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
         const uint32_t opB_lane = opB + 1024u * (uint32_t)(wx + WV * NVW) + 16u * (uint32_t)lane; // this wave's operands in an operand row, tile j: + 1024 j
 
         // ---- the operand pass: block blk0 + k, lane pair (n, n + 32) = target centre vb0 + 32 (blk0 + k) + n --------
-        // tag: register i of a tile holds row m = (i & 3) + 8 (i >> 2) + 4 h of it; smaller m = larger d = preferred
+        // tag: register i of a tile holds row m = (i & 3) + 8 (i >> 2) + 4 h of it; smaller m = larger d = preferred.  The
+        // tag is the pair index i >> 1 (which word of the pair won, the tile's two minimum chains tell); G0 and the
+        // poison ride in it, above the tag bits
         const int blk0 = WV == 0 ? wx : kMfmaXWaves + 2 * wx;
-        uint32_t gsum[NI], btag[NI]; // (window sum of b^^2) + 2 E, modulo 2^32; the tie tag and the poison
+        uint32_t gsum[NI], btag[NI]; // (window sum of b^^2) + 2 E, modulo 2^32; the tie tag, G0 and the poison
 #pragma unroll
         for (int k = 0; k < NI; ++k) {
             const int v = vb0 + 32 * (blk0 + k) + n;
             const bool bvalid = (uint32_t)(v - g.st.b_lo) <= (uint32_t)(g.st.b_hi - g.st.b_lo) && g.st.b_hi >= g.st.b_lo;
-            btag[k] = (uint32_t)((n & 3) + 4 * (n >> 3)) + (bvalid ? 0u : (uint32_t)kPoison);
+            btag[k] = (uint32_t)(((n & 3) >> 1) + 2 * (n >> 3)) + ((uint32_t)(kMfmaG0 + (bvalid ? 0 : kMfmaBiasPoison)) << KT);
             gsum[k] = 0u;
         }
         const uint32_t st_lane = ringB + 3u * (uint32_t)(32 * blk0 + n) + 16u * (uint32_t)h; // this lane's 16 bytes in a raw B row
@@ -334,7 +417,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
             for (int i = 0; i < 16; ++i) {
                 const int m = (i & 3) + 8 * (i >> 2) + 4 * h;
                 const int e = 32 * (NV - 1 - t) + n - m;
-                acc[j][i] = (uint32_t)e <= (uint32_t)dspan ? 0 : kPoison >> (KT + 1);
+                acc[j][i] = (int)((uint32_t)e <= (uint32_t)dspan ? kMfmaA0 : kMfmaA0 + kMfmaAccPoison);
             }
         }
 
@@ -414,7 +497,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
             const int x = tile_x0 + 32 * wx + n, y = ys + sp - (WH - 1);
             if (h == 0 && x < g.ox1) {
                 float val;
-                if (cw >= (kValidKeyBound >> KT)) val = g.fallback_neg ? -(float)x : (float)x; // no valid candidate
+                if (cw >= (int)kMfmaValidBound) val = g.fallback_neg ? -(float)x : (float)x; // no valid candidate
                 else val = (float)(g.d_lo + 32 * (NV - 1) + n - G);
                 if ((__builtin_amdgcn_alignbyte(f.q1, f.q0, f.sh) & 0x00ffffffu) == 0u) val = 0.0f;
                 if (g.out16) g.out16[(size_t)y * g.out_pitch + x] = (int16_t)(int)val;
@@ -465,7 +548,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                     ae = (mfma_raw_align(rae) ^ (int)0x7f7f7f7fu) & amask;
                     if constexpr (PHASE >= 2) al = (mfma_raw_align(ral) ^ (int)0x80808080u) & amask;
                 }
-                int bestk = INT_MAX, bestt = 0;
+                MfmaBest best{UINT_MAX, UINT_MAX, 0u}; // "none": every key is below it
                 const uint32_t brow = biasr + 4u * (uint32_t)((s & 1) * L.nvc + 32 * (wx + WV * NVW) + 4 * h);
                 if constexpr (PIPE) {
                     // ---- the pipelined tile loop (see the header) -----------------------------------------------
@@ -540,21 +623,8 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                             leave(t + 2);
                             __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
                         }
-                        int key[16];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const uint4 b4 = bq[t & 1][q];
-                            key[4 * q + 0] = (int)(((uint32_t)acc[t][4 * q + 0] << (KT + 1)) + b4.x);
-                            key[4 * q + 1] = (int)(((uint32_t)acc[t][4 * q + 1] << (KT + 1)) + b4.y);
-                            key[4 * q + 2] = (int)(((uint32_t)acc[t][4 * q + 2] << (KT + 1)) + b4.z);
-                            key[4 * q + 3] = (int)(((uint32_t)acc[t][4 * q + 3] << (KT + 1)) + b4.w);
-                        }
-                        int km = min(key[0], key[1]);
-#pragma unroll
-                        for (int i = 2; i < 16; i += 2) km = min(min(km, key[i]), key[i + 1]); // one v_min, then 7 v_min3_i32
-                        const bool better = (km | ((1 << KT) - 1)) < bestk;
-                        bestk = better ? km : bestk;
-                        bestt = better ? t : bestt;
+                        if (t == 0) mfma_tile_best<true>(acc[t], bq[t & 1], t, best);
+                        else mfma_tile_best<false>(acc[t], bq[t & 1], t, best);
                     }
                 } else
 #pragma unroll
@@ -571,29 +641,19 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                         acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bl, al, acc[t], 0, 0, 0);
                     }
                     if constexpr (PHASE >= 1) {
-                        int key[16];
+                        uint4 b4[4];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const uint4 b4 = lds_load128(brow + 4u * (uint32_t)(32 * t + 8 * q));
-                            key[4 * q + 0] = (int)(((uint32_t)acc[t][4 * q + 0] << (KT + 1)) + b4.x);
-                            key[4 * q + 1] = (int)(((uint32_t)acc[t][4 * q + 1] << (KT + 1)) + b4.y);
-                            key[4 * q + 2] = (int)(((uint32_t)acc[t][4 * q + 2] << (KT + 1)) + b4.z);
-                            key[4 * q + 3] = (int)(((uint32_t)acc[t][4 * q + 3] << (KT + 1)) + b4.w);
-                        }
-                        int km = min(key[0], key[1]);
-#pragma unroll
-                        for (int i = 2; i < 16; i += 2) km = min(min(km, key[i]), key[i + 1]); // one v_min, then 7 v_min3_i32
-                        // a later tile (smaller d) wins on a strictly smaller cost only
-                        const bool better = (km | ((1 << KT) - 1)) < bestk;
-                        bestk = better ? km : bestk;
-                        bestt = better ? t : bestt;
+                        for (int q = 0; q < 4; ++q) b4[q] = lds_load128(brow + 4u * (uint32_t)(32 * t + 8 * q));
+                        if (ALL && t == 0) mfma_tile_best<true>(acc[t], b4, t, best);
+                        else mfma_tile_best<false>(acc[t], b4, t, best);
                     }
                 }
                 if constexpr (PHASE >= 1) {
                     // the two halves of a column: G = 32 t + m orders ALL its candidates (smaller = larger d)
-                    const int i_best = bestk & ((1 << KT) - 1);
-                    int G = 32 * (bestt + WV * NVW) + (i_best & 3) + 8 * (i_best >> 2) + 4 * h;
-                    int cw = bestk >> KT; // the cost word
+                    const uint32_t bestc = mfma_best_code(best); // 2 t + (the high word of the pair won)
+                    const int i_best = 2 * (int)(best.k & ((1u << KT) - 1u)) + (int)(bestc & 1u);
+                    int G = 32 * ((int)(bestc >> 1) + WV * NVW) + (i_best & 3) + 8 * (i_best >> 2) + 4 * h;
+                    int cw = (int)(best.k >> KT); // the cost word (+ kMfmaC0): below 2^29
                     mfma_pair_best(cw, G);
                     if constexpr (WV == 1 && PHASE >= 2) flush_store(s - 1, fl);
                     // the first wave of a column leaves its best in LDS for the second, which writes the row out in the

@@ -52,9 +52,12 @@ bool march_mfma_plan(const Canon &c, int num_cus, MarchLaunch *out)
     m.tiles = ceil_div(out_w, m.tile_cols);
     m.lds_bytes = (size_t)mfma_lds_layout(c.ww, c.wh).bytes;
     // One workgroup per CU (its accumulators fill the register file): a round of strips is num_cus workgroups.
-    const int strips = best_strips(kMfmaStrips, out_h, m.tiles, c.wh, num_cus).strips;
+    const int forced_rows = march_knobs().mfma_strip_rows;
+    const int strips = forced_rows > 0 ? ceil_div(out_h, forced_rows) : best_strips(kMfmaStrips, out_h, m.tiles, c.wh, num_cus).strips;
     m.strip_rows = ceil_div(out_h, strips);
     m.strips = ceil_div(out_h, m.strip_rows);
+    // the packed key's ranges are derived for strips of up to kMfmaMaxSteps rows entered (ws_march_mfma.h)
+    if (m.strip_rows + c.wh - 1 > kMfmaMaxSteps) return false;
     *out = m;
     return true;
 }

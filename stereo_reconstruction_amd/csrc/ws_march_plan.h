@@ -19,6 +19,8 @@ struct MarchKnobs {
     int stage_agap = 0;          // WS_STAGE_AGAP: image A's stage roles this many places behind image B's
     int mfma = -1;               // WS_MARCH_MFMA: 0 = never the matrix-core SSD kernel, 1 = wherever it can run (whatever the
                                  // search's size)
+    int mfma_strip_rows = 0;     // WS_MFMA_STRIP_ROWS: rows per strip of the matrix-core kernel (> 0), whatever the strip
+                                 // model says: a development knob (one long strip in a small image)
     bool stencil_forced = false; // WS_PLAN_SLOTS, WS_PLAN_THREADS, WS_MAX_CHUNKS or WS_MARCH_ND is set (to anything): the
                                  // stencil kernel's knobs keep meaning the stencil kernel
 };
