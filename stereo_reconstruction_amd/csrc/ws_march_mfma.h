@@ -29,15 +29,18 @@
 // the row out one step later.
 // Rows travel HBM -> LDS as the bytes they are (raw_dma of ws_march_kernel.h) into a ring of WH + 4 raw rows per
 // image, and stay raw: every consumer centres the bytes in an instruction it issues anyway.  One barrier per step:
-//   step s:  copy row s + 3  |  (row s + 2 rests: the copies' look-ahead)  |  row s + 1 of the target image: one pass
-//            makes its lane-linear MFMA operands (a ring of WH + 2 rows of 12 KB) and, from the same registers, the
-//            bias' values (the row's sum of squares stays in the pad of its operand entry and is read back, not computed
-//            again, when the row leaves the windows)  |  MFMAs, keys of row s, output of row s - 1.
+//   step s:  copy row s + 3  |  (row s + 2 rests: the copies' look-ahead)  |  row s + 1 of the target image: its
+//            lane-linear MFMA operands (a ring of WH + 2 rows of 12 KB; a block of 32 centres is 4 v_alignbyte and 4
+//            v_bitop3, centred and masked, on a lane pair per centre) and its bias' values: the sums over a centre's
+//            window bytes are a box over per-pixel sums, formed once per pixel -- a lane a pixel, the neighbours' by
+//            DPP -- and not once per centre that holds the pixel (the window's sum of squares stays in the pad of the
+//            centre's operand entry and is read back, not computed again, when the row leaves the windows)  |  MFMAs,
+//            keys of row s, output of row s - 1.
 // The step ends when its slowest wave reaches the barrier, so the roles are dealt by tile share: the waves with 5 tiles
-// (wv = 0) take one block of the operand pass each and waves 0 and 1 the copies, the waves with 4 tiles (wv = 1) take
-// two blocks each, the merge of the two waves' candidates and the store of the output row.  A wave's role is a template
-// argument of its march, the rows' ring offsets and byte phases are scalars advanced with a compare and a wrap, and the
-// steady phase of a strip has no guard.
+// (wv = 0) take one block of operands each and waves 0 and 1 the copies, the waves with 4 tiles (wv = 1) take two blocks
+// each, the merge of the two waves' candidates and the store of the output row; every wave takes one chunk of 58
+// centres' sums.  A wave's role is a template argument of its march, the rows' ring offsets and byte phases are
+// scalars advanced with a compare and a wrap, and the steady phase of a strip has no guard.
 //
 // The steady step (PHASE 2, and the tile loop of PHASE 3) of the march with every tile active is a software pipeline,
 // pinned with __builtin_amdgcn_sched_barrier / sched_group_barrier because source order alone does not survive the
@@ -50,8 +53,8 @@
 //      that covers what the next instruction consumes and nothing younger;
 //   2. the entering MFMAs of all tiles, then the leaving MFMAs, in four groups (entering 0 .. NTL - 3 | NTL - 2,
 //      NTL - 1 | leaving 0, 1 | then one leaving MFMA per key block): inside a group the compiler may take any order,
-//      and no order puts two MFMAs on one accumulator side by side.  The operand pass's VALU (two halves per block:
-//      items_enter, items_leave) sits between the MFMAs of the first three groups;
+//      and no order puts two MFMAs on one accumulator side by side.  The operand pass's VALU (a block's operands:
+//      items_enter; a chunk's sums in two halves: sums_box, sums_leave) sits between the MFMAs of the first three groups;
 //   3. tile t's keys and minimum run under the leaving MFMA of tile t + 2; the bias quads of tile t + 1 (a double
 //      buffer of 2 x 16 registers) are read a whole key block ahead of their use.  The minimum of the 16 keys is two
 //      chains of 8, min(min(km, a), b): one v_min and 3 v_min3 each (mfma_tile_best);
@@ -176,13 +179,6 @@ __device__ __forceinline__ ws_i32x4 mfma_raw_align(const MfmaRaw &r)
     return v;
 }
 
-// lane n and lane n + 32 both get the sum of their two values: one v_permlane32_swap
-__device__ __forceinline__ uint32_t mfma_pair_sum(uint32_t x)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return r[0] + r[1];
-}
-
 // lane n and lane n + 32 both get the better of their two candidates (smaller cost word, then smaller G): two
 // v_permlane32_swap, no LDS, no branch
 __device__ __forceinline__ void mfma_pair_best(int &cw, int &G)
@@ -198,14 +194,13 @@ __device__ __forceinline__ void mfma_pair_best(int &cw, int &G)
 // The sizes of the VALU groups that sched_group_barrier places behind the MFMAs of the steady step.  They are read off
 // the gfx950 listing, not derived: kPipeValuA = the instructions that make the entering row's A operand in front of
 // the first MFMA (4 v_alignbyte + 4 v_bitop3); kPipeValu[role] = the VALU of the operand pass that lies between the
-// first six MFMAs (about 37 instructions per block: one block on a 5-tile wave, two on a 4-tile wave) divided by the
-// MFMAs it is spread under, rounded up.  A group asks for "up to" its size, so a number that is off, or another
-// compiler's instruction count, regroups the VALU and changes no result; after a toolchain change
-// tools/mfma_listing.py is the check (no neighbouring MFMAs on one accumulator, the read-to-wait distances).
-// (Read again off the listing with the packed keys: the operand pass is what it was, 37 instructions per block with
-// the bias' word still one v_lshl_add_u32, and so are the sizes; the shorter key blocks lie behind these groups.)
+// first six MFMAs divided by the MFMAs it is spread under, rounded up: a block's operands are 8 instructions and its
+// addresses, a chunk's packed window sums 11, its running sum and bias word 9 -- 12 under two MFMAs at the most, on
+// either role.  A group asks for "up to" its size, so a number that is off, or another compiler's instruction count,
+// regroups the VALU and changes no result; after a toolchain change tools/mfma_listing.py is the check (no
+// neighbouring MFMAs on one accumulator, the read-to-wait distances).
 constexpr int kPipeValuA = 8;
-constexpr int kPipeValu[2] = {7, 12};
+constexpr int kPipeValu[2] = {6, 6};
 
 // The keys of a tile and their minimum.  Registers 2 q, 2 q + 1 and their two bias words are aligned 64-bit pairs, and
 // (Acc << 4) + bias' on the pair is both keys (kMfmaKT above: nothing crosses between the words): 8 v_lshl_add_u64.  The
@@ -389,22 +384,43 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
         // tag is the pair index i >> 1 (which word of the pair won, the tile's two minimum chains tell); G0 and the
         // poison ride in it, above the tag bits
         const int blk0 = WV == 0 ? wx : kMfmaXWaves + 2 * wx;
-        uint32_t gsum[NI], btag[NI]; // (window sum of b^^2) + 2 E, modulo 2^32; the tie tag, G0 and the poison
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const int v = vb0 + 32 * (blk0 + k) + n;
-            const bool bvalid = (uint32_t)(v - g.st.b_lo) <= (uint32_t)(g.st.b_hi - g.st.b_lo) && g.st.b_hi >= g.st.b_lo;
-            btag[k] = (uint32_t)(((n & 3) >> 1) + 2 * (n >> 3)) + ((uint32_t)(kMfmaG0 + (bvalid ? 0 : kMfmaBiasPoison)) << KT);
-            gsum[k] = 0u;
-        }
         const uint32_t st_lane = ringB + 3u * (uint32_t)(32 * blk0 + n) + 16u * (uint32_t)h; // this lane's 16 bytes in a raw B row
         const uint32_t it_lane = opB + 1024u * (uint32_t)blk0 + 16u * (uint32_t)lane;         // ... in an operand row
-        const uint32_t bi_lane = biasr + 4u * (uint32_t)(32 * blk0 + n);
-        // An operand entry has room for the row's sum of squares: in the h = 1 lane of a pair dwords 2 and 3 are bytes
+        const uint32_t it_hi = it_lane + (h == 0 ? 8u : 0u); // where the entry's upper 8 bytes go (items_enter)
+        // ---- the row's sums: chunk WV kMfmaXWaves + wx, lane i = pixel cp0 + i of the raw B row = target centre cp0 + i ----
+        // The window of centre v is pixels v .. v + WW - 1 of the raw row, so its sums are a box over per-pixel sums: a
+        // lane forms the sum of squares q of its pixel's 3 centred bytes and the sum r of its 3 raw bytes, packs them
+        // as (q << kSumShift) + r and adds the words of the WW - 1 lanes above it, fetched by DPP inside the additions
+        // (wave_shl:1, lane 63 reads 0).  Lanes 0 .. CW - 1 of a chunk then hold whole windows and own their centres.  The
+        // last chunk starts early enough to stay inside the row, and the eighth wave runs it a second time: a centre with
+        // two owners gets the same words from both (same bytes in, same arithmetic), as the two lanes of a pair wrote the
+        // one bias word before.  Lanes CW .. 63 hold cut windows; the step has no branch, so they store too, into pad
+        // nobody reads (below).
+        constexpr int CW = 64 - (WW - 1), NVC = TX + 32 * (NV - 1), kSumShift = 13;
+        static_assert(WW * 3 * 128 * 128 < (1 << (32 - kSumShift)) && WW * 3 * 255 < (1 << kSumShift), "both window sums fit their fields of the packed word");
+        static_assert((NVC + CW - 1) / CW <= NW && NVC >= CW, "a chunk per wave covers the tile row's centres");
+        const int chunk = WV * kMfmaXWaves + wx;
+        const int cp0 = min(CW * chunk, NVC - CW);
+        const int cv = min(cp0 + lane, NVC - 1); // (lanes past the last centre own nothing; their addresses stay inside the row)
+        const bool c_own = lane < CW;
+        uint32_t gsum = 0u, btag; // (window sum of b^^2) + 2 E, modulo 2^32; the tie tag, G0 and the poison
+        {
+            const int v = vb0 + cv, nn = cv & 31;
+            const bool bvalid = (uint32_t)(v - g.st.b_lo) <= (uint32_t)(g.st.b_hi - g.st.b_lo) && g.st.b_hi >= g.st.b_lo;
+            btag = (uint32_t)(((nn & 3) >> 1) + 2 * (nn >> 3)) + ((uint32_t)(kMfmaG0 + (bvalid ? 0 : kMfmaBiasPoison)) << KT);
+        }
+        const uint32_t cs_lane = ringB + 3u * (uint32_t)(cp0 + lane); // this lane's pixel in a raw B row
+        // An operand entry has room for the window's sum of squares: in the h = 1 lane of a pair dwords 2 and 3 are bytes
         // 24 .. 31 of the centre's 32, which amask zeroes on the A side, so what the B side holds there is multiplied by
-        // zero.  Lane h of the pair keeps its half sum in dword 2 + h of that entry and reads it back when the row leaves.
+        // zero.  The centre's owner keeps the sum in dword 2 of that entry and reads it back when the row leaves.  The
+        // wave that writes the entry is another one, in the same step: its h = 1 lanes store only the 8 bytes that
+        // hold window bytes (items_enter), so the pad has one writer.  Dword 3 is read by nobody: the lanes that own
+        // no centre store their words there, in any row of the ring.
         static_assert(K <= 24, "bytes 24 .. 31 of an operand entry are pad");
-        const uint32_t sq_lane = opB + 1024u * (uint32_t)blk0 + 16u * (uint32_t)(32 + n) + 8u + 4u * (uint32_t)h;
+        const uint32_t pad_lane = opB + 1024u * (uint32_t)(cv >> 5) + 16u * (uint32_t)(32 + (cv & 31)) + 8u;
+        const uint32_t sq_lane = pad_lane + (c_own ? 0u : 4u); // the entering row's sum is written there, the leaving row's read
+        const uint32_t bi_lane = c_own ? biasr + 4u * (uint32_t)cv : pad_lane + 4u;
+        const uint32_t bi_par = c_own ? 4u * (uint32_t)L.nvc : 0u;   // the bias rows are a double buffer
 
         // ---- the accumulators -----------------------------------------------------------------------------------
         // tile t, register i: e = d - d_lo = 32 (NV - 1 - t) + n - m; outside [0, dspan]: poisoned for good
@@ -421,14 +437,16 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
             }
         }
 
-        MfmaRaw ir[NI]; // the entering row's raw bytes
-        uint32_t il[NI]; // the leaving row's half sum of squares, as it was stored when the row entered
+        MfmaRaw ir[NI];          // the entering row's raw bytes: the blocks' ...
+        uint32_t cd0 = 0u, cd1 = 0u, csh = 0u; // ... and the chunk's pixel
+        uint32_t il = 0u;        // the leaving row's window sum of squares, as it was stored when the row entered
         auto items_load = [&](auto leaves) __attribute__((always_inline)) {
 #pragma unroll
-            for (int k = 0; k < NI; ++k) {
-                ir[k] = mfma_raw_load(st_lane + 96u * (uint32_t)k + bSt + phSt);
-                if constexpr (decltype(leaves)::value) il[k] = *lds_at32(sq_lane + 1024u * (uint32_t)k + oSq);
-            }
+            for (int k = 0; k < NI; ++k) ir[k] = mfma_raw_load(st_lane + 96u * (uint32_t)k + bSt + phSt);
+            const uint32_t at = cs_lane + bSt + phSt;
+            const lds_u32 *q = lds_at32(at & ~3u);
+            cd0 = q[0], cd1 = q[1], csh = at & 3u;
+            if constexpr (decltype(leaves)::value) il = *lds_at32(sq_lane + oSq);
         };
         // what a pipelined step reads before the barrier of the step before it (issue order = order of use): the two
         // raw A rows, the leaving row's operands, the operand pass's rows.  None of it is written in that step: the A
@@ -443,37 +461,47 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
             for (int t = 0; t < NTL; ++t) n_bl[t] = lds_load128(opB_lane + oOut + 1024u * (uint32_t)t);
             items_load(std::true_type());
         };
-        // row iu enters the windows of the target centres, row iu - WH leaves them; block k in two parts, so that the
-        // pipelined step can place them under different MFMAs: the entering row's operands and sums ...
-        uint32_t iu_[NI];
+        // row iu enters the windows of the target centres, row iu - WH leaves them; in parts, so that the pipelined step
+        // can place them under different MFMAs: the entering row's operands, block k ...
         auto items_enter = [&](int k) __attribute__((always_inline)) {
-            ws_i32x4 c = mfma_raw_align(ir[k]);
-            c ^= (int)0x80808080u;
-            lds_store128(it_lane + 1024u * (uint32_t)k + oWr, make_uint4((uint32_t)c.x, (uint32_t)c.y, (uint32_t)c.z, (uint32_t)c.w));
-            const ws_i32x4 cm = c & amask; // (the bytes past the window count as zeros)
-            int q = 0, t = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                q = __builtin_amdgcn_sdot4(c[j], cm[j], q, false);
-                t = __builtin_amdgcn_sdot4(cm[j], 0x01010101, t, false);
-            }
-            *reinterpret_cast<lds_u32 *>((uintptr_t)(sq_lane + 1024u * (uint32_t)k + oWr)) = (uint32_t)q; // (behind the entry's own store)
-            iu_[k] = (uint32_t)q + 2u * (uint32_t)t;
+            // centred and masked in one v_bitop3 per dword, as the A operands are: the stored B operand has zeros in its
+            // pad too (the A side multiplies the pad by zero either way)
+            const ws_i32x4 cm = (mfma_raw_align(ir[k]) ^ (int)0x80808080u) & amask;
+            // two stores of 8 bytes, the upper half first: the h = 0 lanes put it behind the lower half, the h = 1 lanes,
+            // whose upper half is pad that belongs to the sums' owner, at the lower half's own address, where the second
+            // store (a wave's LDS operations complete in order) overwrites it
+            *reinterpret_cast<lds_i64 *>((uintptr_t)(it_hi + 1024u * (uint32_t)k + oWr)) = ws_i32x2{cm.z, cm.w};
+            *reinterpret_cast<lds_i64 *>((uintptr_t)(it_lane + 1024u * (uint32_t)k + oWr)) = ws_i32x2{cm.x, cm.y};
         };
-        // ... and the leaving row's sum (read back, not computed again), the lane pair's total and the bias' value
-        auto items_leave = [&](int iu, int k, auto leaves) __attribute__((always_inline)) {
-            uint32_t u = iu_[k];
-            if constexpr (decltype(leaves)::value) u -= il[k];
-            gsum[k] += mfma_pair_sum(u);
-            // (both lanes of a pair write the one word)
-            *reinterpret_cast<lds_u32 *>((uintptr_t)(bi_lane + 4u * (uint32_t)((iu & 1) * L.nvc + 32 * k))) = (gsum[k] << KT) + btag[k];
+        // ... the chunk's packed window sums ...
+        uint32_t cbox = 0u;
+        auto sums_box = [&]() __attribute__((always_inline)) {
+            const uint32_t x = __builtin_amdgcn_alignbyte(cd1, cd0, csh); // the pixel's 3 bytes and one of the next
+            const int c = (int)((x ^ 0x80808080u) & 0x00ffffffu); // (the constant the operands are centred with)
+            const uint32_t q = (uint32_t)__builtin_amdgcn_sdot4(c, c, 0, false);
+            const uint32_t r = __builtin_amdgcn_udot4(x, 0x00010101u, 0u, false);
+            const uint32_t w = (q << kSumShift) + r;
+            uint32_t s = w;
+            // (mov_dpp, not update_dpp(0, ...): see ws_march_kernel.h; the move folds into the addition)
+#pragma unroll
+            for (int j = 1; j < WW; ++j) s = w + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x130, 0xf, 0xf, true); // wave_shl:1
+            cbox = s;
+        };
+        // ... and the leaving row's sum (read back, not computed again), the running total and the bias' value.  A ring
+        // byte outside the image is the byte -128 like any other: r counts it as 0, and sum b^ = r - 128 K.
+        auto sums_leave = [&](int iu, auto leaves) __attribute__((always_inline)) {
+            const uint32_t q = cbox >> kSumShift, r = cbox & ((1u << kSumShift) - 1u);
+            uint32_t u = q + 2u * r - 2u * 128u * (uint32_t)K;
+            if constexpr (decltype(leaves)::value) u -= il;
+            gsum += u;
+            *reinterpret_cast<lds_u32 *>((uintptr_t)(sq_lane + oWr)) = q;
+            *reinterpret_cast<lds_u32 *>((uintptr_t)(bi_lane + (uint32_t)(iu & 1) * bi_par)) = (gsum << KT) + btag;
         };
         auto items_finish = [&](int iu, auto leaves) __attribute__((always_inline)) {
 #pragma unroll
-            for (int k = 0; k < NI; ++k) {
-                items_enter(k);
-                items_leave(iu, k, leaves);
-            }
+            for (int k = 0; k < NI; ++k) items_enter(k);
+            sums_box();
+            sums_leave(iu, leaves);
         };
 
         // ---- the output row of step sp: the better of the two waves' candidates, the fallback, the black-pixel rule ----
@@ -586,7 +614,7 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                     enter(NTL - 2), enter(NTL - 1);
                     if constexpr (STEADY) {
                         if constexpr (NI == 2) items_enter(1);
-                        else items_leave(s + 1, 0, Leaves());
+                        else sums_box();
                     }
                     __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
@@ -597,14 +625,17 @@ __global__ void __launch_bounds__(64 * kMfmaWaves) ws_march_mfma_kernel(const Ma
                         if (stage) { items_load(Leaves()); items_finish(s + 1, Leaves()); }
                     }
                     leave(0), leave(1);
-                    if constexpr (STEADY && NI == 2) items_leave(s + 1, 0, Leaves());
+                    if constexpr (STEADY) {
+                        if constexpr (NI == 2) sums_box();
+                        else sums_leave(s + 1, Leaves());
+                    }
                     __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
                     __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x2, VG, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (STEADY && NI == 2) {
-                        items_leave(s + 1, 1, Leaves());
+                        sums_leave(s + 1, Leaves());
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     advance(); // (nothing below names a cursor of this step)
